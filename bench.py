@@ -18,6 +18,12 @@ scaling, the default; --scaling weak keeps 256 per rank), per-GPU-local replay,
 per update one flat RCCL all-reduce of the small gradients + an all-gather of the
 hidden layer's batch matrices (pfrl_amd/distributed.py).
 
+A plain run sets up, warms up, times --steps steps of the chosen workload and prints its line
+(value, ms_per_step, the roofline of the timed launches).  --full adds everything else the
+line has carried: the other BASELINE.json workloads (``also``), the rank-shaped legs, the
+zero-FLOP data-path figure, the per-launch table of one update, the collective latencies and
+the CPU baselines.  --dump-outputs DIR writes what the last timed step computed as DIR/*.npy.
+
 Prints ONE JSON line on rank 0 (see DESIGN.md section "Measurement").
 """
 import argparse
@@ -116,6 +122,14 @@ def parse_args():
                         "NumPy does (one D2H per update)")
     p.add_argument("--torch-optimizer", action="store_true",
                    help="stock torch.optim.RMSprop instead of the fused HIP step")
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement beyond the headline: the other workloads, "
+                        "rank-shaped legs, data-path-only figure, per-launch table, collective "
+                        "latencies and CPU baselines (the --no-* flags still apply)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (actions, rewards, dones, a fixed "
+                        "sample of the next observations, the networks' parameters, the agent's "
+                        "statistics) as DIR/<name>.npy in float32 / float64, at most 64 MB")
     args = p.parse_args()
     if args.scaling is None:
         args.scaling = "strong"
@@ -251,6 +265,52 @@ def collective_microbench(agent, device, iters=50):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_MAX_ELEMENTS = 1 << 22     # per array; a larger output is written as a fixed, seeded sample
+DUMP_OBS_ENVS = 16              # envs whose next observation is written
+
+
+def _dump_array(x):
+    """float64 stays float64, everything else becomes float32; flattened to a seeded sample of
+    DUMP_MAX_ELEMENTS elements when larger (the same indices on every run)."""
+    if torch.is_tensor(x):
+        x = x.detach().cpu().numpy()
+    elif torch.is_tensor(getattr(x, "tensor", None)):      # DeviceActions
+        x = x.tensor.detach().cpu().numpy()
+    x = np.asarray(x)
+    x = x if x.dtype == np.float64 else x.astype(np.float32)
+    if x.size > DUMP_MAX_ELEMENTS:
+        idx = np.sort(np.random.RandomState(0).choice(x.size, DUMP_MAX_ELEMENTS, replace=False))
+        x = x.reshape(-1)[idx]
+    return x
+
+
+def dump_outputs(path, agent, last):
+    """What the last timed step computed, as a caller of the step receives it: the actions of
+    batch_act, the env's rewards / dones, the next observations of a fixed set of envs, every
+    network of the agent after the step's updates (parameters flattened in module order) and
+    the numeric entries of get_statistics()."""
+    outs = {"actions": last["actions"], "rewards": last["rewards"], "dones": last["dones"]}
+    obs = last["next_obs"]
+    envs = np.sort(np.random.RandomState(0).choice(len(obs), min(len(obs), DUMP_OBS_ENVS),
+                                                   replace=False))
+    outs["next_obs_sample"] = np.stack([np.asarray(obs[int(i)]) for i in envs])
+    outs["next_obs_envs"] = envs
+    for name in getattr(agent, "saved_attributes", ()):
+        m = getattr(agent, name, None)
+        if isinstance(m, torch.nn.Module) and any(True for _ in m.parameters()):
+            outs[name] = torch.cat([p.detach().reshape(-1).float() for p in m.parameters()])
+    for name, v in agent.get_statistics():
+        if isinstance(v, (int, float, np.number)) and not isinstance(v, bool):
+            outs["stat_" + name] = np.float64(v)
+    arrays = {k: _dump_array(v) for k, v in outs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs of %d bytes exceed the dump limit" % total
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def run_workload(args, device, rank, world, result_extras=True):
     """Build, prefill, warm up and time one workload; returns the result dict (rank 0) or None."""
     from pfrl_amd import ops
@@ -315,11 +375,12 @@ def run_workload(args, device, rank, world, result_extras=True):
     torch.cuda.synchronize()
     # (one event per step boundary: where the device time of the timed region goes, step by step)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(min(args.steps, 1024) + 1)]
+    last = {}       # (what the step hands its caller, kept by reference: --dump-outputs)
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
         _tick("timed steps %s" % args.algo)
-        obss = one_step(agent, env, obss, N)
+        obss = one_step(agent, env, obss, N, record=last)
         if i + 1 < len(marks):
             marks[i + 1].record()
     barrier()
@@ -329,6 +390,8 @@ def run_workload(args, device, rank, world, result_extras=True):
     _tick("after timed steps %s" % args.algo)
     ops.profile_enable(False)
     n_updates = updates_done() - optim_before
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(args.dump_outputs, agent, dict(last, next_obs=obss))
 
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64)
@@ -352,6 +415,8 @@ def run_workload(args, device, rank, world, result_extras=True):
                 "device time of ONE optimizer update (forward, TD loss, backward, optimizer step) "
                 "inside the captured %d-update range graph, hipEvents around the replay" % big_u)
             try:
+                if not args.full:
+                    raise RuntimeError("measured with --full only")
                 if args.algo != "dqn" or torch.distributed.is_initialized():
                     raise RuntimeError("measured for the single-process DQN update only")
                 pl = mfma_per_launch(agent, rbuf, args.minibatch)
@@ -375,10 +440,12 @@ def run_workload(args, device, rank, world, result_extras=True):
         from pfrl_amd import rccl
 
         out["config"].update(rccl.status())
-        out["config"]["collective_us"] = collective_microbench(agent, device)
+        if args.full:
+            out["config"]["collective_us"] = collective_microbench(agent, device)
     if args.algo == "rainbow":
         out["config"]["priority_pow"] = rbuf.priority_pow
-    if result_extras and args.algo == "dqn" and not args.host_env and not args.no_data_path_only:
+    if (result_extras and args.full and args.algo == "dqn" and not args.host_env
+            and not args.no_data_path_only):
         # every rank runs it (the agents are symmetric); rank 0 reports its own
         dpo, obss = data_path_only(args, device, agent, env, rbuf, obss, min(args.steps, 100))
         out["data_path_only"] = dpo
@@ -488,12 +555,13 @@ def main():
             return run_workload(*a, **kw)
 
     out = run_guarded(args, device, rank, world)
-    if args.algo == "dqn" and not args.host_env and not args.no_also:
+    if args.full and args.algo == "dqn" and not args.host_env and not args.no_also:
         # the other half of BASELINE.json's metric ("DQN 256 envs, PPO 512 envs"): the PPO
         # configs[3] workload, timed by the same process right after
         import copy
 
         pargs = copy.copy(args)
+        pargs.dump_outputs = None       # (the headline workload's outputs only)
         pargs.algo, pargs.steps, pargs.warmup = "ppo", 128, 128
         pargs.num_envs = 512 if args.scaling == "weak" else 512 // world
         pargs.cudnn_benchmark = False
@@ -519,6 +587,7 @@ def main():
                                                 "--blas", blas]) if own else None
                 if r2 is None:
                     a2 = copy.copy(args)
+                    a2.dump_outputs = None
                     a2.algo, a2.steps, a2.warmup = algo, 50, 20
                     a2.num_envs, a2.minibatch, a2.blas = n_envs, mb, blas
                     a2.cudnn_benchmark = True
@@ -533,7 +602,7 @@ def main():
                     out["also"][algo] = {k: r2[k] for k in keys}
             if own and rank == 0:
                 rank_shape_legs(args, out, keys)
-    if rank == 0:
+    if rank == 0 and args.full:
         if not args.no_cpu_baseline and world == 1 and args.algo == "dqn":
             port = cpu_baseline(args, min(args.cpu_baseline_seconds, 8.0))
             ref = reference_baseline(args)

@@ -166,7 +166,7 @@ def also_in_own_process(args, argv, limit_s=900, extra_env=None):
     import subprocess
 
     cmd = [sys.executable, BENCH] + argv + [
-        "--no-also", "--no-cpu-baseline", "--no-data-path-only", "--seed", str(args.seed)]
+        "--full", "--no-also", "--no-cpu-baseline", "--no-data-path-only", "--seed", str(args.seed)]
     if args.allow_lib_override:
         cmd.append("--allow-lib-override")
     env = dict(os.environ)

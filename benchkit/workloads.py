@@ -270,12 +270,14 @@ def workload_description(args, N, rbuf):
                       N * 128, 32 * N))
 
 
-def one_step(agent, env, obss, num_envs):
+def one_step(agent, env, obss, num_envs, record=None):
     actions = agent.batch_act(obss)
     obss, rs, dones, infos = env.step(actions)
     resets = np.zeros(num_envs, dtype=bool)
     agent.batch_observe(obss, rs, dones, resets)
     not_end = np.logical_not(dones)
+    if record is not None:
+        record["actions"], record["rewards"], record["dones"] = actions, rs, dones
     return env.reset(not_end)
 
 

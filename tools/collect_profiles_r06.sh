@@ -8,7 +8,7 @@ O=$R/gpurun_out/r06
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 has() { [[ " $PARTS " == *" $1 "* ]]; }
-B="python $R/bench.py --no-cpu-baseline"
+B="python $R/bench.py --full --no-cpu-baseline"
 if has dqn; then
   # DQN headline: kernel stats + window summary + one-update timeline
   rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -- \
@@ -102,6 +102,6 @@ fi
 if has line; then
   # the driver's line (after the PMC files of this run have been put where bench.py looks for them)
   for n in gather ppo rainbow sac; do [ -s $O/pmc_$n.json ] && cp $O/pmc_$n.json $R/profiles/r06_pmc_$n.json; done
-  python $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
+  python $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 fi
 ls -la $O

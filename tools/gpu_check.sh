@@ -14,7 +14,7 @@ else
 fi
 tail -8 $O/gpu_tests.txt
 for A in ${ALGOS:-ppo}; do
-  timeout 600 python $R/bench.py --algo $A --no-cpu-baseline ${BENCH_ARGS:-} > $O/bench_$A.json 2> $O/bench_$A.err
+  timeout 600 python $R/bench.py --full --algo $A --no-cpu-baseline ${BENCH_ARGS:-} > $O/bench_$A.json 2> $O/bench_$A.err
   python - <<PY
 import json
 try:

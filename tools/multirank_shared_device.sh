@@ -20,7 +20,7 @@ echo "rccl_multirank_check world=4 pattern=B rc=$?"
 export PFRL_RCCL_SHARED_DEVICE=1 PFRL_BENCH_STALL_S=200
 run() { name=$1; shift
   timeout 400 env "$@" python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $PORT \
-      $R/bench.py --gpus 2 $ARGS > $O/$name.json 2> $O/$name.err
+      $R/bench.py --full --gpus 2 $ARGS > $O/$name.json 2> $O/$name.err
   echo "$name rc=$?"; python - <<PY
 import json
 try:
