@@ -389,32 +389,20 @@ int pfrl_rmsprop_step(int32_t n_tensors, float *const *host_params,
  *   PLAIN         src = the gradient tensor
  *   SLABS         src = first of n_slabs split-K partial slabs, slab_stride floats apart: summed
  *                 while loading (what pfrl_splitk_reduce would have written)
- *   LOWRANK       the weight of a Linear(K, F) layer whose gradient is dy^T x over a batch of M
- *                 rows: src = dy [M][F] (counted where mask [M][F] > 0: the ReLU of the layer's
- *                 output; mask may be NULL), x [M][K]; formed tile by tile on the matrix cores
- *                 (f32 16x16x4 MFMA, exact f32) and applied from the accumulators -- the F x K
- *                 gradient never exists in memory.  K % 64 == 0, F % 16 == 0, M % 4 == 0, M <= 32
- *   LOWRANK_BIAS  that layer's bias: sum over the M rows of the masked dy column
  *   FOLD          no parameter: out[i] = sum of the slabs (loss terms that rode on the fold)
  * host_tasks is a host array (copied into the kernel arguments: graph-capturable). */
 #define PFRL_OPT_MAX_TASKS 16
 #define PFRL_OPT_PLAIN 0
 #define PFRL_OPT_SLABS 1
-#define PFRL_OPT_LOWRANK 2
-#define PFRL_OPT_LOWRANK_BIAS 3
 #define PFRL_OPT_FOLD 4
 typedef struct {
     float *p, *sq, *ga;     /* parameter, square_avg, grad_avg (centered) */
     const float *src;
     float *out;             /* FOLD */
-    const float *mask;      /* LOWRANK / LOWRANK_BIAS */
-    const float *x;         /* LOWRANK */
     int64_t numel;
     int64_t slab_stride;
     int32_t n_slabs;
     int32_t mode;
-    int32_t M, F, K;
-    int32_t reserved;
 } pfrl_opt_task_t;
 int pfrl_rmsprop_fused_step(int32_t n_tasks, const pfrl_opt_task_t *host_tasks, float lr,
                             float alpha, float eps, float weight_decay, int centered, void *stream);
@@ -595,7 +583,7 @@ int pfrl_conv2d_u8nhwc4_bwd_weight(const float *dy, const float *dy_mask, const 
  * latency-bound workgroups; by then the gradients of the layers above are final (ride_grad[i],
  * finished tensors) and their parameters are not read again in this update, so their
  * elementwise steps (the arithmetic of pfrl_rmsprop_step) run as extra workgroups of this launch.
- * 1 <= n_ride <= 8 HOST arrays of device pointers (plus whatever pfrl_ride_set left pending); 16-byte aligned, numel % 4 == 0;
+ * 1 <= n_ride <= 8 HOST arrays of device pointers; 16-byte aligned, numel % 4 == 0;
  * ride_grad_avg may be NULL when centered == 0.  The caller must not step these tensors again. */
 int pfrl_conv2d_nhwc_bwd_weight_ride(
     const float *dy, const float *dy_mask, const float *x, float *dw_part, float *db_part,
@@ -604,20 +592,6 @@ int pfrl_conv2d_nhwc_bwd_weight_ride(
     const float *const *ride_grad, float *const *ride_square_avg, float *const *ride_grad_avg,
     const int64_t *ride_numel, float lr, float alpha, float eps, float weight_decay, int centered,
     void *stream);
-/* Optimizer steps (the arithmetic of pfrl_rmsprop_step) handed to the NEXT backward launch of this
- * host thread -- pfrl_conv2d_nhwc_bwd or pfrl_conv2d_nhwc_bwd_weight_ride -- which runs them as extra
- * workgroups and clears the set (pfrl/agents/dqn.py:360-365 `loss.backward(); optimizer.step()` at
- * minibatch size: by the time a layer's backward launch starts, the gradient of the layer above
- * is complete and its parameters are not read again in the update).  Up to 8 tensors; the
- * gradient of tensor i is grad_src[i] itself (n_slabs[i] == 0) or the sum, in slab order, of
- * n_slabs[i] split-K slabs slab_stride[i] floats apart (what pfrl_conv2d_nhwc_bwd_weight /
- * pfrl_dqn_head_td_loss leave).  n == 0 clears the set.  A pfrl_conv2d_nhwc_bwd whose tile
- * program has no riding form returns an error WITHOUT launching (and clears the set): the caller
- * launches again and steps those tensors elsewhere. */
-int pfrl_ride_set(int32_t n, float *const *param, const float *const *grad_src,
-                  float *const *square_avg, float *const *grad_avg, const int64_t *numel,
-                  const int32_t *n_slabs, const int64_t *slab_stride, float lr, float alpha, float eps,
-                  float weight_decay, int centered);
 /* Both gradients of one layer in ONE launch (same dy): arguments of _bwd_data and _bwd_weight
  * combined.  Minibatch-sized problems only; returns PFRL_ERR_ARG for larger ones (the caller
  * then issues the two launches). */

@@ -116,12 +116,9 @@ class OptTask(ctypes.Structure):
 
     _fields_ = [
         ("p", ctypes.c_void_p), ("sq", ctypes.c_void_p), ("ga", ctypes.c_void_p),
-        ("src", ctypes.c_void_p), ("out", ctypes.c_void_p), ("mask", ctypes.c_void_p),
-        ("x", ctypes.c_void_p),
+        ("src", ctypes.c_void_p), ("out", ctypes.c_void_p),
         ("numel", ctypes.c_int64), ("slab_stride", ctypes.c_int64),
         ("n_slabs", ctypes.c_int32), ("mode", ctypes.c_int32),
-        ("M", ctypes.c_int32), ("F", ctypes.c_int32), ("K", ctypes.c_int32),
-        ("reserved", ctypes.c_int32),
     ]
 
 
@@ -203,7 +200,6 @@ EXPORTS = {
     "pfrl_conv2d_nhwc_bwd_weight": (ctypes.c_int, "pppppqqiiiiiiiiip"),
     "pfrl_conv2d_nhwc_bwd_weight_ride": (ctypes.c_int, "pppppqqiiiiiiiiiipppppffffip"),
     "pfrl_conv2d_nhwc_bwd": (ctypes.c_int, "ppppppppqqiiiiiiiiiiip"),
-    "pfrl_ride_set": (ctypes.c_int, "ippppppp" + "ffffi"),
     "pfrl_splitk_reduce": (ctypes.c_int, "ippppppppp"),
     "pfrl_splitk_reduce_noisy": (ctypes.c_int, "ippppppppppp"),
     "pfrl_splitk_group": (ctypes.c_int, "pqiiipqp"),

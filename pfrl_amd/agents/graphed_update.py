@@ -245,9 +245,6 @@ class GraphedUpdate:
             if defer:
                 mfma_trunk.OPT_SOURCES = {}
                 mfma_trunk.RIDE_ALONG = self.agent.optimizer
-                # (the head's per-row partials may ride in a backward launch too: which parameter
-                # each of the queued folds belongs to)
-                mfma_trunk.RIDE_HEAD = {g.data_ptr(): p for p, g in head if p.requires_grad}
                 # data parallel: a layer whose gradient is exchanged as its batch matrices is
                 # stepped where the product is formed, on the communicator's side stream
                 red.lowrank_step = self._step_on_side_stream
@@ -258,7 +255,6 @@ class GraphedUpdate:
             finally:
                 mfma_trunk.OPT_SOURCES = None
                 mfma_trunk.RIDE_ALONG = None
-                mfma_trunk.RIDE_HEAD = None
                 red.lowrank_step = None
             if defer and sources:
                 # the head's per-row partials (queued by the loss launch for "the fold that ends

@@ -764,7 +764,7 @@ class PPO(agent.AttributeSavingMixin, agent.BatchAgent):
         ``obs_normalizer``) pick kernels by batch size: no guarantee, the full pass runs."""
         from pfrl_amd.nn import mfma_trunk
 
-        if os.environ.get("PFRL_PPO_DEDUP_NEXT", "1") == "0" or self.obs_normalizer is not None:
+        if self.obs_normalizer is not None:
             return 0
         chunk = int(self.value_pass_chunk)
         if not (M <= chunk or M % chunk == 0):

@@ -340,8 +340,6 @@ class PrioritizedBuffer:
         d = self._deferred
         if d is None or more_pending or os.environ.get("PFRL_TREE_FUSE_SAMPLE", "1") == "0":
             return False
-        if os.environ.get("PFRL_TREE_SAMPLE") not in (None, "", "prefetch"):
-            return False
         L = self.frame.log2_size
         return (n_draws >= 1 and d[0].numel() + int(n_writes or 0) <= 64 and 1 <= L <= 22
                 and L - min(L, 9) + 1 <= 13)

@@ -248,7 +248,7 @@ extern "C" int pfrl_batch_states_u8(const void *frames, int64_t frame_bytes, con
                                     int64_t n_refs, float divisor, float *out, void *stream) {
     PFRL_CHECK_ARG(frame_bytes > 0 && (frame_bytes & 3) == 0, "frame_bytes must be a multiple of 4");
     if (n_refs <= 0) return 0;
-    const bool nt = n_refs * frame_bytes * 4 >= pfrl_nt_min_bytes();
+    const bool nt = n_refs * frame_bytes * 4 >= kNtMinBytes;
     const dim3 grid((unsigned)n_refs), block(kThreads);
     hipStream_t st = (hipStream_t)stream;
     const uint8_t *fr = (const uint8_t *)frames;
@@ -278,7 +278,7 @@ extern "C" int pfrl_batch_states_u8_nhwc4(const void *frames, int64_t frame_byte
     PFRL_CHECK_ARG(frame_bytes > 0 && (frame_bytes & 3) == 0, "frame_bytes must be a multiple of 4");
     if (n_obs <= 0) return 0;
     const int tiles = (int)((frame_bytes + pfrl_nhwc::kTilePixels - 1) / pfrl_nhwc::kTilePixels);
-    const bool nt = n_obs * 4 * frame_bytes * 4 >= pfrl_nt_min_bytes();
+    const bool nt = n_obs * 4 * frame_bytes * 4 >= kNtMinBytes;
     const dim3 grid((unsigned)(n_obs * tiles)), block(kThreads);
     hipStream_t st = (hipStream_t)stream;
     const uint8_t *fr = (const uint8_t *)frames;

@@ -686,14 +686,10 @@ extern "C" int pfrl_gae_scan(int64_t T, int64_t N, const double *reward, const f
     hipEvent_t e0 = nullptr, e1 = nullptr;
     pfrl_profile_events(PFRL_PROFILE_GAE_SCAN, T * N, &e0, &e1);
     // rollouts that fit a workgroup's LDS (T * E envs * 9 or 13 bytes <= 64 KB)
-    // take the LDS-staged form; PFRL_GAE_LDS=0 keeps the lane-per-env loop for A/B runs
-    static const bool use_lds = [] {
-        const char *e = getenv("PFRL_GAE_LDS");
-        return !(e != nullptr && e[0] == '0');
-    }();
+    // take the LDS-staged form; larger ones the lane-per-env loop
     const int E = N >= 4096 ? 16 : 8;
     const size_t lds = (size_t)T * E * ((mode == 0 ? 4 : 8) + 4 + 1);
-    if (use_lds && lds <= 64 * 1024 && T < (1 << 20)) {
+    if (lds <= 64 * 1024 && T < (1 << 20)) {
         const unsigned blocks = (unsigned)((N + E - 1) / E);
 #define PFRL_GAE_LAUNCH(MODE_, E_)                                                                   \
     hipExtLaunchKernelGGL((k_gae_scan_lds<MODE_, E_>), dim3(blocks), dim3(kThreads), lds,            \

@@ -517,339 +517,23 @@ __global__ __launch_bounds__(64) void k_tree_sample(pfrl_tree_t T, int64_t B,
     }
 }
 
-// ---------------------------------------------------------------------------
-// LDS-staged sampler.  The B draws are sequentially dependent, so the cost is
-// a latency chain; this version shortens every link of it:
-//   * the top of the tree (levels L .. r, r = min(L, 9)) is copied once into an
-//     LDS heap (<= 8192 nodes, 72 KB) and stays authoritative for the whole
-//     launch: 12 of the 21 levels of a 1M-leaf tree descend at LDS latency;
-//   * the 2^(r+1)-1 nodes below the chosen level-r node are fetched by the 64
-//     lanes in ONE parallel round trip into a second LDS heap, so the bottom
-//     r levels also descend at LDS latency (instead of r dependent HBM/L2
-//     round trips);
-//   * the zero-and-repair pass runs on the LDS copies and the touched path is
-//     written back to HBM by one lane per level.
-// Arithmetic and visiting order are exactly those of k_tree_sample.
-// ---------------------------------------------------------------------------
 #ifdef PFRL_TREE_DEBUG
-__device__ unsigned long long g_dbg[8];
-#define DBG_T(k) do { if (lane == 0) { unsigned long long t__ = wall_clock64(); g_dbg[k] += t__ - t_prev; t_prev = t__; } } while (0)
-#else
-#define DBG_T(k)
+__device__ unsigned long long g_dbg[8];   // phase clocks of k_tree_sample_lean2 (tools/per_dbg2.py)
 #endif
 
 constexpr int kBotLevels = 9;   // r: bottom subtree root level
 constexpr int kMaxTopLog2 = 13; // top heap holds levels L..r, at most 13 levels
 
-__global__ __launch_bounds__(64) void k_tree_sample_lds(
-    pfrl_tree_t T, int64_t B, const double *__restrict__ u01, int64_t *__restrict__ out_x,
-    double *__restrict__ out_pri, uint8_t *__restrict__ out_pri_tag, double *__restrict__ out_prob,
-    float *__restrict__ out_weight, double *__restrict__ out_total,
-    uint8_t *__restrict__ out_total_tag, double *__restrict__ out_min_prob, int normalize,
-    double beta, int64_t slot_mod, int32_t *__restrict__ out_slot) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int L = T.log2_size;
-    const int r = L < kBotLevels ? L : kBotLevels;
-    const int top_levels = L - r + 1;           // levels L..r  -> depths 0..top_levels-1
-    const int top_n = 1 << top_levels;          // heap indices 1..top_n-1
-    const int bot_n = 1 << (r + 1);             // heap indices 1..bot_n-1 (levels r..0)
-    double *top_v = reinterpret_cast<double *>(smem);
-    double *bot_v = top_v + top_n;
-    uint8_t *top_t = reinterpret_cast<uint8_t *>(bot_v + bot_n);
-    uint8_t *bot_t = top_t + top_n;
-    __shared__ double s_total_v, s_min_v;
-    __shared__ int s_total_t, s_min_t;
-    // per-level addressing constants (kernel-argument arrays indexed per lane would
-    // otherwise become memory loads in the hot loops)
-    __shared__ int64_t lv_off[PFRL_MAX_LEVELS], lv_org[PFRL_MAX_LEVELS], lv_mask[PFRL_MAX_LEVELS];
-    const int lane = threadIdx.x;
-    if (lane <= L) {
-        const int sh = T.log2_smax - lane;
-        lv_off[lane] = T.level_off[lane];
-        lv_org[lane] = T.origin[lane];
-        lv_mask[lane] = (sh > 0 ? ((int64_t)1 << sh) : 1) - 1;
-    }
-    __syncthreads();
-#define NODE_AT(l, x) (lv_off[l] + ((((x) - lv_org[l]) >> (l)) & lv_mask[l]))
-
-    // stage the top of the sum tree (loads batched 16 deep per lane)
-    for (int h0 = 1; h0 < top_n; h0 += 64 * 16) {
-        double v[16];
-        uint8_t tg[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int h = h0 + k * 64 + lane;
-            if (h < top_n) {
-                const int d = 31 - __clz(h);
-                const int l = L - d;
-                const int64_t gi = NODE_AT(l, T.base + ((int64_t)(h - (1 << d)) << l));
-                v[k] = T.sum_val[gi];
-                tg[k] = T.sum_tag[gi];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int h = h0 + k * 64 + lane;
-            if (h < top_n) {
-                top_v[h] = v[k];
-                top_t[h] = tg[k];
-            }
-        }
-    }
-    if (lane == 0) {
-        const int64_t iroot = NODE_AT(L, T.base);
-        s_total_v = T.sum_val[iroot];
-        s_total_t = T.sum_tag[iroot];
-        s_min_v = T.min_val[iroot];
-        s_min_t = T.min_tag[iroot];
-    }
-    __syncthreads();
-
-#ifdef PFRL_TREE_DEBUG
-    unsigned long long t_prev = wall_clock64();
-    if (lane == 0) for (int k = 0; k < 8; ++k) g_dbg[k] = 0;
-#endif
-    for (int64_t i = 0; i < B; ++i) {
-        // siblings met on the way down, kept in registers for the repair pass
-        double sv[kMaxTopLog2 + kBotLevels];
-        int st[kMaxTopLog2 + kBotLevels];
-        bool went_right[kMaxTopLog2 + kBotLevels];
-        // ---- descend the top heap (every lane computes the same path) ----
-        TV root = mk_tv(top_v[1], top_t[1]);
-        TV pos = mk_tv(__dadd_rn(0.0, __dmul_rn(root.v, u01[i])), PFRL_TAG_PY);
-        int h = 1;
-        // Two levels per LDS round trip: the children AND the four grandchildren of h
-        // are requested together (12 independent LDS reads), then both decisions are
-        // taken in registers.  The dependent chain is what this kernel pays for, and
-        // an LDS read (~100 ns) is most of a level.
-#pragma unroll
-        for (int d = 0; d < kMaxTopLog2 - 1; d += 2) {
-            if (d < top_levels - 1) {
-                const bool two = d + 1 < top_levels - 1;       // uniform
-                const int gbase = two ? 4 * h : 2 * h;          // always inside the heap
-                const double cv0 = top_v[2 * h], cv1 = top_v[2 * h + 1];
-                const int ct0 = top_t[2 * h], ct1 = top_t[2 * h + 1];
-                const double gv0 = top_v[gbase], gv1 = top_v[gbase + 1];
-                const double gv2 = top_v[gbase + (two ? 2 : 0)], gv3 = top_v[gbase + (two ? 3 : 1)];
-                const int gt0 = top_t[gbase], gt1 = top_t[gbase + 1];
-                const int gt2 = top_t[gbase + (two ? 2 : 0)], gt3 = top_t[gbase + (two ? 3 : 1)];
-                {
-                    TV lc = mk_tv(cv0, ct0), rc = mk_tv(cv1, ct1);
-                    TV left = lc.t != PFRL_TAG_ABSENT ? lc : mk_tv(0.0, PFRL_TAG_PY);
-                    const bool go_left = tv_lt(pos, left);
-                    if (!go_left) pos = tv_sub(pos, left);
-                    sv[d] = go_left ? rc.v : lc.v;
-                    st[d] = go_left ? rc.t : lc.t;
-                    went_right[d] = !go_left;
-                    h = 2 * h + (go_left ? 0 : 1);
-                }
-                if (d + 1 < kMaxTopLog2 - 1 && two) {
-                    const bool was_left = !went_right[d];
-                    TV lc = mk_tv(was_left ? gv0 : gv2, was_left ? gt0 : gt2);
-                    TV rc = mk_tv(was_left ? gv1 : gv3, was_left ? gt1 : gt3);
-                    TV left = lc.t != PFRL_TAG_ABSENT ? lc : mk_tv(0.0, PFRL_TAG_PY);
-                    const bool go_left = tv_lt(pos, left);
-                    if (!go_left) pos = tv_sub(pos, left);
-                    sv[d + 1] = go_left ? rc.v : lc.v;
-                    st[d + 1] = go_left ? rc.t : lc.t;
-                    went_right[d + 1] = !go_left;
-                    h = 2 * h + (go_left ? 0 : 1);
-                }
-            }
-        }
-        const int64_t x0 = T.base + ((int64_t)(h - (top_n >> 1)) << r);
-        DBG_T(0);
-        // ---- fan-out: the whole subtree below in one parallel round trip ----
-        // level l of the subtree is 2^(r-l) consecutive ring slots: lanes read
-        // consecutive addresses (coalesced), all loads issued before any use.
-        {
-            double v[8 + 4 + 2 + kBotLevels - 2];
-            uint8_t tg[8 + 4 + 2 + kBotLevels - 2];
-            // slot numbering below is a compile-time function of (l, k): the
-            // arrays stay in registers
-            int n_ld = 0;
-#pragma unroll
-            for (int l = 0; l <= kBotLevels; ++l) {
-                const int lr = l <= r ? l : r;               // clamp (uniform)
-                const int cnt = l <= r ? (1 << (r - l)) : 0;
-                const int64_t q0 = (x0 - lv_org[lr]) >> lr;
-                const int64_t off = lv_off[lr], mask = lv_mask[lr];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (k * 64 < (1 << (kBotLevels - l))) {
-                        // unconditional load from a clamped (always valid) slot: keeps
-                        // all loads in one basic block so they are issued back to back
-                        const int j = k * 64 + lane;
-                        const int64_t gi = off + ((q0 + (j < cnt ? j : 0)) & mask);
-                        v[n_ld] = T.sum_val[gi];
-                        tg[n_ld] = T.sum_tag[gi];
-                        ++n_ld;
-                    }
-                }
-            }
-            n_ld = 0;
-#pragma unroll
-            for (int l = 0; l <= kBotLevels; ++l) {
-                const int cnt = l <= r ? (1 << (r - l)) : 0;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (k * 64 < (1 << (kBotLevels - l))) {
-                        const int j = k * 64 + lane;
-                        if (j < cnt) {
-                            bot_v[cnt + j] = v[n_ld];   // heap index of (level l, j)
-                            bot_t[cnt + j] = tg[n_ld];
-                        }
-                        ++n_ld;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        DBG_T(1);
-        // ---- descend the bottom heap ----
-        int g = 1;
-#pragma unroll
-        for (int d = 0; d < kBotLevels; d += 2) {
-            if (d < r) {
-                const bool two = d + 1 < r;                     // uniform
-                const int gbase = two ? 4 * g : 2 * g;
-                const double cv0 = bot_v[2 * g], cv1 = bot_v[2 * g + 1];
-                const int ct0 = bot_t[2 * g], ct1 = bot_t[2 * g + 1];
-                const double gv0 = bot_v[gbase], gv1 = bot_v[gbase + 1];
-                const double gv2 = bot_v[gbase + (two ? 2 : 0)], gv3 = bot_v[gbase + (two ? 3 : 1)];
-                const int gt0 = bot_t[gbase], gt1 = bot_t[gbase + 1];
-                const int gt2 = bot_t[gbase + (two ? 2 : 0)], gt3 = bot_t[gbase + (two ? 3 : 1)];
-                {
-                    TV lc = mk_tv(cv0, ct0), rc = mk_tv(cv1, ct1);
-                    TV left = lc.t != PFRL_TAG_ABSENT ? lc : mk_tv(0.0, PFRL_TAG_PY);
-                    const bool go_left = tv_lt(pos, left);
-                    if (!go_left) pos = tv_sub(pos, left);
-                    sv[kMaxTopLog2 + d] = go_left ? rc.v : lc.v;
-                    st[kMaxTopLog2 + d] = go_left ? rc.t : lc.t;
-                    went_right[kMaxTopLog2 + d] = !go_left;
-                    g = 2 * g + (go_left ? 0 : 1);
-                }
-                if (d + 1 < kBotLevels && two) {
-                    const bool was_left = !went_right[kMaxTopLog2 + d];
-                    TV lc = mk_tv(was_left ? gv0 : gv2, was_left ? gt0 : gt2);
-                    TV rc = mk_tv(was_left ? gv1 : gv3, was_left ? gt1 : gt3);
-                    TV left = lc.t != PFRL_TAG_ABSENT ? lc : mk_tv(0.0, PFRL_TAG_PY);
-                    const bool go_left = tv_lt(pos, left);
-                    if (!go_left) pos = tv_sub(pos, left);
-                    sv[kMaxTopLog2 + d + 1] = go_left ? rc.v : lc.v;
-                    st[kMaxTopLog2 + d + 1] = go_left ? rc.t : lc.t;
-                    went_right[kMaxTopLog2 + d + 1] = !go_left;
-                    g = 2 * g + (go_left ? 0 : 1);
-                }
-            }
-        }
-        const int64_t x = x0 + (g - (bot_n >> 1));
-        const double leaf_v = bot_v[g];
-        const uint8_t leaf_t = bot_t[g];
-        __syncthreads();
-        DBG_T(2);
-        // ---- zero the leaf, repair the path from the remembered siblings ----
-        TV cur = mk_tv(0.0, PFRL_TAG_PY);
-        if (lane == 0) {
-            out_x[i] = x;
-            out_pri[i] = leaf_v;
-            out_pri_tag[i] = leaf_t;
-            bot_v[g] = 0.0;
-            bot_t[g] = PFRL_TAG_PY;
-        }
-        int c = g;
-#pragma unroll
-        for (int d = kBotLevels - 1; d >= 0; --d) {
-            if (d < r) {
-                TV sib = mk_tv(sv[kMaxTopLog2 + d], st[kMaxTopLog2 + d]);
-                cur = reduce_sum(cur, sib);   // IEEE add commutes, so operand order is immaterial
-                c >>= 1;
-                if (lane == 0) {
-                    bot_v[c] = cur.v;
-                    bot_t[c] = (uint8_t)cur.t;
-                }
-            }
-        }
-        c = h;
-        if (lane == 0) {
-            top_v[c] = cur.v;
-            top_t[c] = (uint8_t)cur.t;
-        }
-#pragma unroll
-        for (int d = kMaxTopLog2 - 2; d >= 0; --d) {
-            if (d < top_levels - 1) {
-                TV sib = mk_tv(sv[d], st[d]);
-                cur = reduce_sum(cur, sib);
-                c >>= 1;
-                if (lane == 0) {
-                    top_v[c] = cur.v;
-                    top_t[c] = (uint8_t)cur.t;
-                }
-            }
-        }
-        __syncthreads();
-        DBG_T(3);
-        // ---- write the touched path back to HBM: one lane per level ----
-        if (lane <= L) {
-            const int l = lane;
-            double v;
-            uint8_t tg;
-            if (l <= r) {
-                const int gg = g >> l;          // ancestor of the leaf at level l
-                v = bot_v[gg];
-                tg = bot_t[gg];
-            } else {
-                const int hh = h >> (l - r);
-                v = top_v[hh];
-                tg = top_t[hh];
-            }
-            const int64_t gi = NODE_AT(l, x);
-            T.sum_val[gi] = v;
-            T.sum_tag[gi] = tg;
-        }
-        __syncthreads();
-        DBG_T(4);
-    }
-#undef NODE_AT
-    if (lane == 0) {
-        *out_total = s_total_v;
-        *out_total_tag = (uint8_t)s_total_t;
-    }
-    __threadfence_block();
-    __syncthreads();
-    const TV total = mk_tv(s_total_v, s_total_t);
-    double local_min = __builtin_huge_val();
-    for (int64_t i = lane; i < B; i += 64) {
-        TV pr = tv_add(mk_tv(0.0, PFRL_TAG_PY), tv_div(mk_tv(out_pri[i], out_pri_tag[i]), total));
-        out_prob[i] = pr.v;
-        local_min = fmin(local_min, pr.v);
-    }
-    for (int off = 32; off > 0; off >>= 1) local_min = fmin(local_min, __shfl_xor(local_min, off));
-    double min_prob = tv_div(mk_tv(s_min_v, s_min_t), total).v;
-    if (lane == 0) *out_min_prob = min_prob;
-    if (normalize == 1) min_prob = local_min;
-    for (int64_t i = lane; i < B; i += 64) {
-        const double p = out_prob[i];
-        double w;
-        if (normalize)
-            w = pow(p / min_prob, -beta);
-        else
-            w = pow((double)T.length * p, -beta);
-        out_weight[i] = (float)w;
-        if (out_slot) out_slot[i] = (int32_t)(out_x[i] % slot_mod);
-    }
-}
-
-
 // ---------------------------------------------------------------------------
-// Lean sampler (round 4).  Same arithmetic, same visiting order, same results as
-// k_tree_sample; what changes is the number of instructions on the chain.  The
-// kernel is ONE wave, and a wave issues at most one instruction -- of any kind --
-// every four clocks: k_tree_sample_lds spends ~70 instructions per level on
-// branch-free typed arithmetic (both candidate types evaluated, selects) and
-// ~50 per level of the repair, i.e. it is bound by instruction issue, not by
-// LDS latency (in-kernel clocks: 157 ns per level).
-//
+// LDS sampler (k_tree_sample_lean2).  Same arithmetic, same visiting order, same
+// results as k_tree_sample.  The B draws are sequentially dependent, so the cost is
+// a latency chain, and the kernel shortens every link of it:
+//   * the top of the tree (levels L .. r, r = min(L, 9)) is copied once into an
+//     LDS heap (<= 8192 nodes) and stays authoritative for the whole launch; the
+//     2^(r+1)-1 nodes below the chosen level-r node are fetched by the 64 lanes in
+//     ONE parallel round trip into a second LDS heap, so the bottom r levels also
+//     descend at LDS latency.  What remains is bound by instruction issue (a wave
+//     issues one instruction every four clocks), so each level is kept short:
 //   * descent: almost every level is an np.float32 operation -- the position is
 //     np.float32 after its first subtraction, and NEP 50 makes f32 (op) python
 //     float a float32 operation on the float32-rounded values; an absent left child
@@ -953,249 +637,9 @@ __device__ __forceinline__ int find_down(const double *hv, const uint8_t *ht, in
     return h;
 }
 
-__global__ __launch_bounds__(64) void k_tree_sample_lean(
-    pfrl_tree_t T, int64_t B, const double *__restrict__ u01, int64_t *__restrict__ out_x,
-    double *__restrict__ out_pri, uint8_t *__restrict__ out_pri_tag, double *__restrict__ out_prob,
-    float *__restrict__ out_weight, double *__restrict__ out_total,
-    uint8_t *__restrict__ out_total_tag, double *__restrict__ out_min_prob, int normalize,
-    double beta, int64_t slot_mod, int32_t *__restrict__ out_slot) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int L = T.log2_size;
-    const int r = L < kBotLevels ? L : kBotLevels;
-    const int top_levels = L - r + 1;           // levels L..r  -> depths 0..top_levels-1
-    const int top_n = 1 << top_levels;          // heap indices 1..top_n-1
-    const int bot_n = 1 << (r + 1);             // heap indices 1..bot_n-1 (levels r..0)
-    double *top_v = reinterpret_cast<double *>(smem);
-    double *bot_v = top_v + top_n;
-    uint8_t *top_t = reinterpret_cast<uint8_t *>(bot_v + bot_n);
-    uint8_t *bot_t = top_t + top_n;
-    __shared__ double s_total_v, s_min_v;
-    __shared__ int s_total_t, s_min_t;
-    __shared__ int64_t lv_off[PFRL_MAX_LEVELS], lv_org[PFRL_MAX_LEVELS], lv_mask[PFRL_MAX_LEVELS];
-    const int lane = threadIdx.x;
-    if (lane <= L) {
-        const int sh = T.log2_smax - lane;
-        lv_off[lane] = T.level_off[lane];
-        lv_org[lane] = T.origin[lane];
-        lv_mask[lane] = (sh > 0 ? ((int64_t)1 << sh) : 1) - 1;
-    }
-    if (lane == 0) {
-        // heap index 0 is never a node; the pair (0, 1) is never requested either, but keep it defined
-        top_v[0] = 0.0;
-        top_t[0] = 0;
-        bot_v[0] = 0.0;
-        bot_t[0] = 0;
-    }
-    __syncthreads();
-#define NODE_AT(l, x) (lv_off[l] + ((((x) - lv_org[l]) >> (l)) & lv_mask[l]))
-    // my own level's addressing constants (lane l owns level l in the repair / write-back)
-    const int myl = lane <= L ? lane : 0;
-    const int64_t my_off = lv_off[myl], my_org = lv_org[myl], my_mask = lv_mask[myl];
-
-    // stage the top of the sum tree (loads batched 16 deep per lane)
-    for (int h0 = 1; h0 < top_n; h0 += 64 * 16) {
-        double v[16];
-        uint8_t tg[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int h = h0 + k * 64 + lane;
-            if (h < top_n) {
-                const int d = 31 - __clz(h);
-                const int l = L - d;
-                const int64_t gi = NODE_AT(l, T.base + ((int64_t)(h - (1 << d)) << l));
-                v[k] = T.sum_val[gi];
-                tg[k] = T.sum_tag[gi];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int h = h0 + k * 64 + lane;
-            if (h < top_n) {
-                top_v[h] = v[k];
-                top_t[h] = tg[k];
-            }
-        }
-    }
-    if (lane == 0) {
-        const int64_t iroot = NODE_AT(L, T.base);
-        s_total_v = T.sum_val[iroot];
-        s_total_t = T.sum_tag[iroot];
-        s_min_v = T.min_val[iroot];
-        s_min_t = T.min_tag[iroot];
-    }
-    __syncthreads();
-
-#ifdef PFRL_TREE_DEBUG
-    unsigned long long t_prev = wall_clock64();
-    if (lane == 0) for (int k = 0; k < 8; ++k) g_dbg[k] = 0;
-#endif
-    double my_u = 0.0;
-    for (int64_t i = 0; i < B; ++i) {
-        // the draws of this launch, 64 at a time, one per lane (a scalar load per draw would be
-        // a memory round trip on the chain)
-        if ((i & 63) == 0) my_u = i + lane < B ? u01[i + lane] : 0.0;
-        const double u = readlane_f64(my_u, (int)(i & 63));
-        // ---- top heap: L - r levels ----
-        const TV root = mk_tv(top_v[1], top_t[1]);
-        // np.random.uniform(0.0, root) = 0.0 + (root - 0.0) * u
-        double p64 = __dadd_rn(0.0, __dmul_rn(root.v, u));
-        float p32 = (float)p64;
-        int pt = PFRL_TAG_PY;
-        const int h = find_down(top_v, top_t, 1, L - r, p64, p32, pt);
-        const int64_t x0 = T.base + ((int64_t)(h - (top_n >> 1)) << r);
-        DBG_T(0);
-        // ---- fan-out: the whole subtree below in one parallel round trip ----
-        {
-            double v[8 + 4 + 2 + kBotLevels - 2];
-            uint8_t tg[8 + 4 + 2 + kBotLevels - 2];
-            int n_ld = 0;
-#pragma unroll
-            for (int l = 0; l <= kBotLevels; ++l) {
-                const int lr = l <= r ? l : r;               // clamp (uniform)
-                const int cnt = l <= r ? (1 << (r - l)) : 0;
-                // level constants from the lane that owns the level: scalar registers, and the
-                // slot of the subtree's first node of the level is scalar arithmetic
-                const int64_t org = readlane_i64(my_org, lr);
-                const int64_t off = readlane_i64(my_off, lr), mask = readlane_i64(my_mask, lr);
-                const int64_t q0 = (x0 - org) >> lr;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (k * 64 < (1 << (kBotLevels - l))) {
-                        const int j = k * 64 + lane;
-                        const int64_t gi = off + ((q0 + (j < cnt ? j : 0)) & mask);
-                        v[n_ld] = T.sum_val[gi];
-                        tg[n_ld] = T.sum_tag[gi];
-                        ++n_ld;
-                    }
-                }
-            }
-            n_ld = 0;
-#pragma unroll
-            for (int l = 0; l <= kBotLevels; ++l) {
-                const int cnt = l <= r ? (1 << (r - l)) : 0;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (k * 64 < (1 << (kBotLevels - l))) {
-                        const int j = k * 64 + lane;
-                        if (j < cnt) {
-                            bot_v[cnt + j] = v[n_ld];   // heap index of (level l, j)
-                            bot_t[cnt + j] = tg[n_ld];
-                        }
-                        ++n_ld;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        DBG_T(1);
-        // ---- bottom heap: r levels ----
-        const int g = find_down(bot_v, bot_t, 1, r, p64, p32, pt);
-        const int64_t x = x0 + (g - (bot_n >> 1));
-        const double leaf_v = bot_v[g];
-        const uint8_t leaf_t = bot_t[g];
-        // ---- the siblings of the path: lane l reads the one of level l ----
-        int st = PFRL_TAG_ABSENT;
-        double sv = 0.0;
-        if (lane < L) {
-            const bool below = lane < r;
-            const int node = below ? (g >> lane) : (h >> (lane - r));     // path node of level `lane`
-            const double *sib_v = below ? bot_v : top_v;
-            const uint8_t *sib_t = below ? bot_t : top_t;
-            st = sib_t[node ^ 1];
-            sv = sib_v[node ^ 1];
-        }
-        if (st == PFRL_TAG_ABSENT) sv = 0.0;      // (an absent child adds nothing; its slot may hold anything)
-        DBG_T(2);
-        if (lane == 0) {
-            out_x[i] = x;
-            out_pri[i] = leaf_v;
-            out_pri_tag[i] = leaf_t;
-        }
-        // ---- zero the leaf, re-reduce the path: lane l holds the sibling of level l ----
-        const float sv32 = (float)sv;
-        const unsigned long long m2 = __ballot(st >= PFRL_TAG_F32);
-        const unsigned long long m3 = __ballot(st == PFRL_TAG_F64);
-        const int l2 = m2 ? __builtin_ctzll(m2) : L;    // first sibling that makes the sum f32 (or f64)
-        const int l3 = m3 ? __builtin_ctzll(m3) : L;    // first sibling that makes it f64
-        double c64 = 0.0, mine64 = 0.0;
-        float c32 = 0.0f, mine32 = 0.0f;
-        int j = 0;
-        for (; j < l2; ++j) {                 // Python floats: f64 adds
-            c64 = __dadd_rn(c64, readlane_f64(sv, j));
-            if (lane == j + 1) mine64 = c64;
-        }
-        if (l2 < l3) {
-            c32 = (float)c64;
-            for (; j < l3; ++j) {             // np.float32 result type: f32 adds of the f32 operands
-                c32 = __fadd_rn(c32, readlane_f32(sv32, j));
-                if (lane == j + 1) mine32 = c32;
-            }
-            c64 = (double)c32;
-        }
-        for (; j < L; ++j) {                  // np.float64 result type
-            c64 = __dadd_rn(c64, readlane_f64(sv, j));
-            if (lane == j + 1) mine64 = c64;
-        }
-        DBG_T(3);
-        // ---- lane l owns the node of level l: top heap + HBM ----
-        if (lane <= L) {
-            const int l = lane;
-            double v;
-            int tg;
-            if (l == 0) {
-                v = 0.0;
-                tg = PFRL_TAG_PY;
-            } else {
-                tg = l > l3 ? PFRL_TAG_F64 : (l > l2 ? PFRL_TAG_F32 : PFRL_TAG_PY);
-                v = tg == PFRL_TAG_F32 ? (double)mine32 : mine64;
-            }
-            if (l >= r) {
-                const int hh = h >> (l - r);
-                top_v[hh] = v;
-                top_t[hh] = (uint8_t)tg;
-            }
-            const int64_t gi = my_off + (((x - my_org) >> l) & my_mask);
-            T.sum_val[gi] = v;
-            T.sum_tag[gi] = (uint8_t)tg;
-        }
-        __syncthreads();          // stores visible to the next draw's fan-out, heaps settled
-        DBG_T(4);
-    }
-#undef NODE_AT
-    if (lane == 0) {
-        *out_total = s_total_v;
-        *out_total_tag = (uint8_t)s_total_t;
-    }
-    __threadfence_block();
-    __syncthreads();
-    const TV total = mk_tv(s_total_v, s_total_t);
-    double local_min = __builtin_huge_val();
-    for (int64_t i = lane; i < B; i += 64) {
-        TV pr = tv_add(mk_tv(0.0, PFRL_TAG_PY), tv_div(mk_tv(out_pri[i], out_pri_tag[i]), total));
-        out_prob[i] = pr.v;
-        local_min = fmin(local_min, pr.v);
-    }
-    for (int off = 32; off > 0; off >>= 1) local_min = fmin(local_min, __shfl_xor(local_min, off));
-    double min_prob = tv_div(mk_tv(s_min_v, s_min_t), total).v;
-    if (lane == 0) *out_min_prob = min_prob;
-    if (normalize == 1) min_prob = local_min;
-    for (int64_t i = lane; i < B; i += 64) {
-        const double p = out_prob[i];
-        double w;
-        if (normalize)
-            w = pow(p / min_prob, -beta);
-        else
-            w = pow((double)T.length * p, -beta);
-        out_weight[i] = (float)w;
-        if (out_slot) out_slot[i] = (int32_t)(out_x[i] % slot_mod);
-    }
-}
-
-
 // ---------------------------------------------------------------------------
-// Lean sampler with a prefetching second wave.  What is left on the chain of
-// k_tree_sample_lean is the fetch of the 1023-node subtree under the level-9
-// node a draw reaches (1.7 us of 5.5, almost all of it memory latency), and it
+// The prefetching second wave of k_tree_sample_lean2.  What is left on the chain of
+// one wave is the fetch of the 1023-node subtree under the level-9 node a draw reaches (1.7 us of 5.5, almost all of it memory latency), and it
 // cannot start before the draw's own top descent has finished.  It can be
 // PREDICTED, though: draw i + 1 starts from root_i * u, and root_i differs from
 // the root before draw i by one leaf out of a million, so a descent of the top
@@ -1205,9 +649,8 @@ __global__ __launch_bounds__(64) void k_tree_sample_lean(
 // descends the top heap exactly, as before; if it arrives where wave 1 predicted
 // AND no earlier draw of this launch went through that subtree (its zeroed leaf
 // would be missing from a fetch issued before or beside the write-back), the
-// subtree is already in LDS; otherwise it fetches it itself, exactly as
-// k_tree_sample_lean does.  The prediction decides where bytes are fetched from
-// early, never what is computed: results are those of k_tree_sample bit for bit.
+// subtree is already in LDS; otherwise it fetches it itself.  The prediction decides
+// where bytes are fetched from early, never what is computed: results are those of k_tree_sample bit for bit.
 // One workgroup barrier per draw (both waves, top of the loop).
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void wave_lds_fence() {
@@ -1705,45 +1148,17 @@ extern "C" int pfrl_tree_sample(const pfrl_tree_t *tree, int64_t B, const double
     if (B == 0) return 0;
     const int L = tree->log2_size;
     const int r = L < kBotLevels ? L : kBotLevels;
-    // PFRL_TREE_SAMPLE: "prefetch" (default) = lean sampler + prefetching wave, "lean" = without it,
-    // "lds" = the round-2 sampler, "global" = global-memory descent
-    static int mode = -1;
-    if (mode < 0) {
-        const char *e = getenv("PFRL_TREE_SAMPLE");
-        const char *old = getenv("PFRL_TREE_SAMPLE_LDS");
-        mode = 3;
-        if (e && e[0] == 'l' && e[1] == 'e') mode = 2;
-        if (e && e[0] == 'l' && e[1] == 'd') mode = 1;
-        if ((e && e[0] == 'g') || (old && old[0] == '0')) mode = 0;
-    }
-    if (mode && L - r + 1 <= kMaxTopLog2) {
+    if (L - r + 1 <= kMaxTopLog2) {
         const size_t top_n = (size_t)1 << (L - r + 1), bot_n = (size_t)1 << (r + 1);
-        const size_t lds = (top_n + bot_n) * (sizeof(double) + 1);
-        const size_t lds2 = (top_n + 2 * bot_n) * (sizeof(double) + 1);
+        const size_t lds = (top_n + 2 * bot_n) * (sizeof(double) + 1);
         static unsigned long long attr_seen = 0;
-        if (attr_needed(&attr_seen)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tree_sample_lds),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tree_sample_lean),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+        if (attr_needed(&attr_seen))
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tree_sample_lean2),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024);
-        }
-        if (mode == 3)
-            hipLaunchKernelGGL(k_tree_sample_lean2, dim3(1), dim3(128), lds2, (hipStream_t)stream,
-                               *tree, B, u01, out_x, out_pri, out_pri_tag, out_prob, out_weight,
-                               out_total, out_total_tag, out_min_prob, normalize, beta,
-                               slot_mod > 0 ? slot_mod : 1, out_slot);
-        else if (mode == 2)
-            hipLaunchKernelGGL(k_tree_sample_lean, dim3(1), dim3(64), lds, (hipStream_t)stream,
-                               *tree, B, u01, out_x, out_pri, out_pri_tag, out_prob, out_weight,
-                               out_total, out_total_tag, out_min_prob, normalize, beta,
-                               slot_mod > 0 ? slot_mod : 1, out_slot);
-        else
-            hipLaunchKernelGGL(k_tree_sample_lds, dim3(1), dim3(64), lds, (hipStream_t)stream, *tree,
-                               B, u01, out_x, out_pri, out_pri_tag, out_prob, out_weight, out_total,
-                               out_total_tag, out_min_prob, normalize, beta,
-                               slot_mod > 0 ? slot_mod : 1, out_slot);
+        hipLaunchKernelGGL(k_tree_sample_lean2, dim3(1), dim3(128), lds, (hipStream_t)stream,
+                           *tree, B, u01, out_x, out_pri, out_pri_tag, out_prob, out_weight,
+                           out_total, out_total_tag, out_min_prob, normalize, beta,
+                           slot_mod > 0 ? slot_mod : 1, out_slot);
     } else {
         hipLaunchKernelGGL(k_tree_sample, dim3(1), dim3(64), 0, (hipStream_t)stream, *tree, B, u01,
                            out_x, out_pri, out_pri_tag, out_prob, out_weight, out_total,

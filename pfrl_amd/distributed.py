@@ -430,12 +430,9 @@ class GradientAllReducer:
         replay correctly (one, several, grouped), while ANY collective on a stream that joined the
         capture through an event wait takes the process down with SIGSEGV inside
         hipStreamEndCapture -- grouped or not, with or without other collectives on the origin
-        stream.  A captured update therefore gives up the overlap (PFRL_DP_FORK_IN_CAPTURE=1
-        restores the fork for a stack where it works)."""
-        cur = torch.cuda.current_stream(device)
-        if (torch.cuda.is_current_stream_capturing()
-                and os.environ.get("PFRL_DP_FORK_IN_CAPTURE", "0") != "1"):
-            return cur
+        stream.  A captured update therefore gives up the overlap."""
+        if torch.cuda.is_current_stream_capturing():
+            return torch.cuda.current_stream(device)
         return self._comm.side
 
     def _finish_lowrank(self):

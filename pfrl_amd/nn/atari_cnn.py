@@ -3,8 +3,6 @@ On the GPU with channels_last weights and ReLU the trunk runs as the hand-writte
 MFMA kernels of csrc/qnet.hip (pfrl_amd/nn/mfma_trunk.py); any other configuration
 takes stock PyTorch-ROCm (MIOpen conv + hipBLASLt GEMM) with the fused bias + ReLU
 launches below."""
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -60,30 +58,13 @@ def conv_activation(layer, h, activation, planar_out=False):
     return activation(layer(h))
 
 
-# Measured on the DQN bench: 16.4 k env-steps/s with this fusion vs 17.7 k without (the
-# GEMM without its bias epilogue takes a slower hipBLASLt kernel than the one it
-# replaces), so it is off unless PFRL_FUSE_LINEAR=1.
-_FUSE_LINEAR = os.environ.get("PFRL_FUSE_LINEAR", "0") == "1"
-
-
 def linear_activation(layer, h, activation):
-    """``activation(layer(h))`` for a linear layer: at minibatch sizes on the GPU the
-    bias add + ReLU (forward) and ReLU mask + bias gradient (backward) are one launch
-    each next to the GEMMs."""
-    if (_FUSE_LINEAR and _is_relu(activation) and h.is_cuda and h.dtype == torch.float32
-            and h.dim() == 2 and isinstance(layer, nn.Linear) and layer.bias is not None
-            and h.shape[0] <= 256 and layer.out_features % 4 == 0):
-        from pfrl_amd import ops
-
-        z = F.linear(h, layer.weight)
-        if ops.bias_relu_supported(z, layer.bias):
-            return ops.bias_relu(z, layer.bias)
-        return activation(z + layer.bias)
+    """``activation(layer(h))`` for a linear layer (a noisy one with its ReLU fused)."""
     from pfrl_amd.nn.noisy_linear import FactorizedNoisyLinear
 
     if isinstance(layer, FactorizedNoisyLinear) and _is_relu(activation):
         return layer(h, relu=True)
-    return activation(layer(h))   # large batches: the GEMM's own bias epilogue
+    return activation(layer(h))
 
 
 class _Identity(nn.Module):

@@ -251,19 +251,6 @@ def _fused_bwd_ok(N, H, W, C, ST):
     return True
 
 
-# The hidden layer's weight gradient formed INSIDE the optimizer launch (GradSource.lowrank) is
-# off by default: measured on MI355X (profiles/r03_fused_optimizer.txt) the weight-gradient half
-# of the hidden layer's fused backward launch is nearly free (dgrad + wgrad 14.0 us, dgrad alone
-# 12.2 us), while the optimizer launch grows from 13 to 22-34 us when it has to build the tiles.
-_LOWRANK = os.environ.get("PFRL_FUSED_OPT_LOWRANK", "0") == "1"
-
-
-def _lowrank_ok(M, F, K, w):
-    from pfrl_amd.optimizers import GradSource
-
-    return w.is_contiguous() and GradSource.lowrank_supported(M, F, K)
-
-
 def _dist_initialized():
     d = torch.distributed
     return d.is_available() and d.is_initialized()
@@ -324,9 +311,8 @@ def _reduce(tasks):
 
 # Set to a dict by a caller whose optimizer finishes the gradients itself
 # (pfrl_amd.optimizers.FusedRMSprop.step_from_sources, GraphedUpdate): the backward pass then
-# hands over split-K slabs and the hidden layer's batch matrices as GradSource objects, keyed by
-# the parameter's data_ptr(), instead of folding / forming the gradients -- and returns None as
-# the gradient of those parameters.
+# hands over split-K slabs as GradSource objects, keyed by the parameter's data_ptr(), instead of
+# folding them into gradients -- and returns None as the gradient of those parameters.
 OPT_SOURCES = None
 # An optimizer (FusedRMSprop) whose steps may RIDE in the last backward launch: set next to
 # OPT_SOURCES by GraphedUpdate.  The hidden layer's weight and bias (95 % of the parameters; their
@@ -335,19 +321,6 @@ OPT_SOURCES = None
 # launch (pfrl_conv2d_nhwc_bwd_weight_ride) and marked GradSource.done() for the optimizer launch.
 RIDE_ALONG = None
 _RIDE = os.environ.get("PFRL_RIDE_ALONG", "1") != "0"
-# Round 6, measured and NOT the default (PFRL_RIDE_MORE=1 turns it on): EVERY finished layer's step
-# riding in the next backward launch (pfrl_ride_set) -- the head's in the last convolution's
-# backward launch, each convolution's in the launch of the layer below it, the optimizer's own
-# launch left with the first convolution and the loss fold.  Bit-identical
-# (tests/test_fused_optimizer.py), and slower: update 84.8 -> 87.8 us, 41.5 -> 40.4 k env-steps/s on
-# one box, twice (profiles/r06_ride_more.txt).  The residual launch does not get shorter -- it is
-# the 50-slab sum of the first convolution either way, 7 dependent round trips on 8 workgroups --
-# while three launches that are latency-bound at 1-3 workgroups per CU each gain slab-summing
-# workgroups and 0.5 KB of arguments.
-# RIDE_HEAD: {gradient tensor data_ptr: parameter} of the narrow head, set next to RIDE_ALONG by
-# GraphedUpdate (the head's per-row partials sit in _DEFERRED_FOLDS).
-RIDE_HEAD = None
-_RIDE_MORE = os.environ.get("PFRL_RIDE_MORE", "0") == "1"
 
 # dh.data_ptr() -> (dh with the hidden layer's ReLU mask applied and scaled by 1 / world, world):
 # left by the fused head + TD-loss launch of a data-parallel update (ops._DQNHeadTDLoss) for the
@@ -545,18 +518,6 @@ class _Trunk(torch.autograd.Function):
                 announce_grad(wf, dwf)
             grads = [None] * (2 * L) + [dwf, dbf]
             return _Trunk._conv_backward(ctx, specs, params, acts, x, dy, N, dev, grads)
-        if OPT_SOURCES is not None and _LOWRANK and _lowrank_ok(N, F, Kf, wf):
-            # the optimizer forms dW = dh^T x itself, tile by tile, and applies it from the
-            # accumulators (csrc/optim.hip): only the input gradient is computed here
-            from pfrl_amd.optimizers import GradSource
-
-            check(lib.pfrl_conv2d_nhwc_bwd_data(_p(dh), _p(out), _p(wf), _p(acts[-1]), _p(dy), N, 1, 1,
-                                                Kf, F, 1, 1, 1, P, last.Cout, _stream()),
-                  "linear_bwd_data")
-            OPT_SOURCES[wf.data_ptr()] = GradSource.lowrank(dh, out, acts[-1].view(N, Kf))
-            OPT_SOURCES[params[2 * L + 1].data_ptr()] = GradSource.lowrank_bias(dh, out)
-            grads = [None] * (2 * L + 2)
-            return _Trunk._conv_backward(ctx, specs, params, acts, x, dy, N, dev, grads)
         if _dist_initialized():
             from pfrl_amd.distributed import announce_grad, announce_lowrank, lowrank_wanted
 
@@ -618,17 +579,6 @@ class _Trunk(torch.autograd.Function):
         lib = _native.lib()
         L = len(specs)
         tasks = []
-        # steps waiting for the next backward launch: [(parameter, dense gradient or GradSource)]
-        riding = (ride is not None and _RIDE_MORE and RIDE_ALONG is not None and OPT_SOURCES is not None
-                  and hasattr(RIDE_ALONG, "ride_set"))
-        carry = []
-        if riding and RIDE_HEAD and _DEFERRED_FOLDS:
-            from pfrl_amd.optimizers import GradSource
-
-            for t in list(_DEFERRED_FOLDS):
-                p_ = RIDE_HEAD.get(t[1].data_ptr())
-                if p_ is not None and len(carry) < 4:
-                    carry.append((p_, GradSource.slabs(t[0], t[3], t[5]), t))
         for i in range(L - 1, -1, -1):
             sp = specs[i]
             w = params[2 * i]
@@ -657,19 +607,9 @@ class _Trunk(torch.autograd.Function):
                 grads[2 * i], grads[2 * i + 1] = None, None
             if i > 0 and _fused_bwd_ok(N, sp.H, sp.W, sp.C, sp.ST):
                 dx = torch.empty((N, sp.H, sp.W, sp.C), dtype=torch.float32, device=dev)
-                bwd_args = (_p(dy), None, _p(w), _p(below), _p(below), _p(dx), _p(pw), _p(pb), st, st, N,
-                            sp.H, sp.W, sp.C, sp.Cout, sp.R, sp.S, sp.ST, 0, 0, splits, _stream())
-                rode = False
-                if carry and RIDE_ALONG.ride_set([(p_, g_) for p_, g_, _ in carry]):
-                    # (a tile program without a riding form refuses BEFORE launching and drops the set)
-                    rode = lib.pfrl_conv2d_nhwc_bwd(*bwd_args) == 0
-                if not rode:
-                    check(lib.pfrl_conv2d_nhwc_bwd(*bwd_args), "conv2d_nhwc_bwd")
-                carry = _after_ride(carry, rode)
-                if riding and splits > 1 and OPT_SOURCES is not None:
-                    # this layer's own step: in the launch of the layer below
-                    carry += [(w, OPT_SOURCES[w.data_ptr()], None),
-                              (params[2 * i + 1], OPT_SOURCES[params[2 * i + 1].data_ptr()], None)]
+                check(lib.pfrl_conv2d_nhwc_bwd(_p(dy), None, _p(w), _p(below), _p(below), _p(dx), _p(pw),
+                                               _p(pb), st, st, N, sp.H, sp.W, sp.C, sp.Cout, sp.R, sp.S,
+                                               sp.ST, 0, 0, splits, _stream()), "conv2d_nhwc_bwd")
                 dy = dx
                 continue
             ra = RIDE_ALONG.ride_arrays([(p_, g_) for p_, g_, _ in ride]) if (ride and i == 0) else None
@@ -677,12 +617,9 @@ class _Trunk(torch.autograd.Function):
                 # the last launch of the backward pass: the finished layers' optimizer steps ride in it
                 from pfrl_amd.optimizers import GradSource
 
-                more = bool(carry) and len(carry) + len(ride) <= 8 and \
-                    RIDE_ALONG.ride_set([(p_, g_) for p_, g_, _ in carry])
                 check(lib.pfrl_conv2d_nhwc_bwd_weight_ride(
                     _p(dy), None, _p(below), _p(pw), _p(pb), st, st, N, sp.H, sp.W, sp.C, sp.Cout, sp.R,
                     sp.S, sp.ST, splits, *ra, _stream()), "conv2d_nhwc_bwd_weight_ride")
-                carry = _after_ride(carry, more)
                 for p_, g_, slot in ride:
                     OPT_SOURCES[p_.data_ptr()] = GradSource.done()
                     grads[slot] = None
@@ -710,21 +647,6 @@ class _Trunk(torch.autograd.Function):
         if tasks:
             _reduce(tasks)
         return (None, None) + tuple(grads)
-
-
-def _after_ride(carry, rode):
-    """Bookkeeping behind a backward launch that carried (``rode``) or did not carry the steps of
-    ``carry``: carried parameters are marked done for the optimizer launch, and the head's
-    deferred folds they came from are withdrawn.  Returns the new (empty) carry list; what did not
-    ride stays with the optimizer launch, as before."""
-    if rode:
-        from pfrl_amd.optimizers import GradSource
-
-        for p_, _, task in carry:
-            OPT_SOURCES[p_.data_ptr()] = GradSource.done()
-            if task is not None and task in _DEFERRED_FOLDS:
-                _DEFERRED_FOLDS.remove(task)
-    return []
 
 
 def trunk_forward(x, specs, convs, linear):

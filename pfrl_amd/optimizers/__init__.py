@@ -18,45 +18,29 @@ def _dense(t):
     return t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))
 
 
-OPT_PLAIN, OPT_SLABS, OPT_LOWRANK, OPT_LOWRANK_BIAS, OPT_FOLD = 0, 1, 2, 3, 4   # PFRL_OPT_*
+OPT_PLAIN, OPT_SLABS, OPT_FOLD = 0, 1, 4   # PFRL_OPT_*
 OPT_DONE = -1     # (host side only: GradSource.done())
 
 
 class GradSource:
     """A gradient in the form the backward pass left it (see ``pfrl_rmsprop_fused_step``):
-    ``slabs(part, stride, n)`` = split-K partial slabs still to be summed; ``lowrank(dy, mask, x)``
-    = the weight of a Linear layer as the product dy^T x of its batch matrices; ``lowrank_bias(dy,
-    mask)`` = that layer's bias.  Tensors are kept alive by the source."""
+    ``slabs(part, stride, n)`` = split-K partial slabs still to be summed.  Tensors are kept alive
+    by the source."""
 
-    __slots__ = ("mode", "src", "mask", "x", "stride", "n_slabs", "M", "F", "K")
+    __slots__ = ("mode", "src", "stride", "n_slabs")
 
-    def __init__(self, mode, src, mask=None, x=None, stride=0, n_slabs=0, M=0, F=0, K=0):
-        self.mode, self.src, self.mask, self.x = mode, src, mask, x
-        self.stride, self.n_slabs, self.M, self.F, self.K = stride, n_slabs, M, F, K
+    def __init__(self, mode, src, stride=0, n_slabs=0):
+        self.mode, self.src, self.stride, self.n_slabs = mode, src, stride, n_slabs
 
     @classmethod
     def slabs(cls, part, stride, n_slabs):
         return cls(OPT_SLABS, part, stride=int(stride), n_slabs=int(n_slabs))
 
     @classmethod
-    def lowrank(cls, dy, mask, x):
-        M, F = dy.shape
-        return cls(OPT_LOWRANK, dy, mask=mask, x=x, M=int(M), F=int(F), K=int(x.shape[1]))
-
-    @classmethod
-    def lowrank_bias(cls, dy, mask):
-        M, F = dy.shape
-        return cls(OPT_LOWRANK_BIAS, dy, mask=mask, M=int(M), F=int(F))
-
-    @classmethod
     def done(cls):
         """The parameter was already stepped in this update (its RMSprop step rode in a backward
         launch, ``FusedRMSprop.ride_arrays``): the optimizer launch skips it."""
         return cls(OPT_DONE, None)
-
-    @staticmethod
-    def lowrank_supported(M, F, K):
-        return K % 64 == 0 and F % 16 == 0 and M % 4 == 0 and 4 <= M <= 32
 
 
 class FusedRMSprop(torch.optim.RMSprop):
@@ -105,56 +89,6 @@ class FusedRMSprop(torch.optim.RMSprop):
                 float(group["lr"]), float(group["alpha"]), float(group["eps"]),
                 float(group["weight_decay"]), int(centered))
 
-    def ride_set(self, entries):
-        """Hand the steps of ``entries`` = [(parameter, gradient)] -- gradient: a finished dense
-        tensor or a ``GradSource.slabs`` -- to the NEXT backward launch of this thread
-        (``pfrl_ride_set``: consumed by ``pfrl_conv2d_nhwc_bwd`` / ``..._bwd_weight_ride``, which run
-        them as extra workgroups).  True = set; the caller then marks the parameters
-        ``GradSource.done()``.  False = a tensor is outside what the kernel covers (nothing set)."""
-        if not self.accepts_sources() or not 1 <= len(entries) <= 8:
-            return False
-        group = self.param_groups[0]
-        centered = bool(group["centered"])
-        rows = []
-        for p, g in entries:
-            st = self.state[p]
-            if len(st) == 0:
-                st["step"] = (torch.zeros((), dtype=torch.float32, device=p.device)
-                              if group.get("capturable", False) else torch.tensor(0.0))
-                st["square_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                if centered:
-                    st["grad_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            sq = st["square_avg"]
-            ga = st["grad_avg"] if centered else None
-            if isinstance(g, GradSource):
-                if g.mode != OPT_SLABS or g.stride % 4 != 0:
-                    return False
-                src, n_slabs, stride = g.src, g.n_slabs, g.stride
-            else:
-                if g.stride() != p.stride() or g.dtype != torch.float32:
-                    return False
-                src, n_slabs, stride = g, 0, 0
-            ts = [p, sq] + ([ga] if centered else [])
-            if not all(t.is_cuda and t.dtype == torch.float32 and _dense(t) and t.stride() == p.stride()
-                       and t.data_ptr() % 16 == 0 for t in ts) or src.data_ptr() % 16 != 0:
-                return False
-            if p.numel() == 0:
-                return False
-            rows.append((p.data_ptr(), src.data_ptr(), sq.data_ptr(), ga.data_ptr() if centered else 0,
-                         p.numel(), n_slabs, stride))
-        n = len(rows)
-        V = ctypes.c_void_p * n
-        rc = _native.lib().pfrl_ride_set(
-            n, V(*[r[0] for r in rows]), V(*[r[1] for r in rows]), V(*[r[2] for r in rows]),
-            V(*[r[3] for r in rows]), (ctypes.c_int64 * n)(*[r[4] for r in rows]),
-            (ctypes.c_int32 * n)(*[r[5] for r in rows]), (ctypes.c_int64 * n)(*[r[6] for r in rows]),
-            float(group["lr"]), float(group["alpha"]), float(group["eps"]),
-            float(group["weight_decay"]), int(centered))
-        return rc == 0
-
-    def ride_clear(self):
-        _native.lib().pfrl_ride_set(0, None, None, None, None, None, None, None, 0.0, 0.0, 0.0, 0.0, 0)
-
     def step_from_sources(self, sources, folds=()):
         """``step()`` where the gradient of parameter ``p`` is ``sources[p]`` (a GradSource) if
         present and ``p.grad`` otherwise; ``folds`` = (part, out, stride, n_slabs) slab sums with
@@ -186,12 +120,7 @@ class FusedRMSprop(torch.optim.RMSprop):
                 t.mode, t.src = OPT_PLAIN, g.data_ptr()
             else:
                 t.mode, t.src = src.mode, src.src.data_ptr()
-                t.mask = src.mask.data_ptr() if src.mask is not None else None
-                t.x = src.x.data_ptr() if src.x is not None else None
                 t.slab_stride, t.n_slabs = src.stride, src.n_slabs
-                t.M, t.F, t.K = src.M, src.F, src.K
-                if src.mode in (OPT_LOWRANK, OPT_LOWRANK_BIAS):
-                    assert p.is_contiguous()
                 keep.append(src)
             tasks.append(t)
         for part, out, stride, n_slabs in folds:

@@ -1,5 +1,5 @@
 """FusedRMSprop.step_from_sources (csrc/optim.hip k_rmsprop_fused): the optimizer step that takes
-gradients as the backward pass left them -- split-K slabs, the hidden layer's batch matrices --
+gradients as the backward pass left them -- split-K slabs --
 against torch.optim.RMSprop fed the materialised gradients (reference: the ``optimizer.step()``
 of pfrl/agents/dqn.py:360-365 with examples/atari/train_dqn_batch_ale.py:199-206's RMSprop)."""
 import copy
@@ -13,12 +13,12 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("centered", [True, False])
-def test_step_from_sources_equals_torch_rmsprop(centered):
+def test_step_from_slab_and_plain_sources_equals_torch_rmsprop(centered):
     from pfrl_amd.optimizers import FusedRMSprop, GradSource
 
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    M, F, K = 32, 128, 192
+    F, K = 128, 192
     shapes = dict(plain=(300,), slabs=(64, 33), w=(F, K), b=(F,))
     params = {k: torch.nn.Parameter(torch.randn(s, device=dev)) for k, s in shapes.items()}
     ref_params = {k: torch.nn.Parameter(p.detach().clone()) for k, p in params.items()}
@@ -30,22 +30,21 @@ def test_step_from_sources_equals_torch_rmsprop(centered):
         S, n = 5, 64 * 33
         stride = n + 40
         part = torch.randn(S * stride, device=dev)
-        dy = torch.randn(M, F, device=dev)
-        out = torch.randn(M, F, device=dev)          # the layer's ReLU output: mask = out > 0
-        x = torch.randn(M, K, device=dev)
+        w_stride = F * K + 8
+        w_part = torch.randn(S * w_stride, device=dev)
+        g_b = torch.randn(F, device=dev)
         fold_part = torch.randn(4 * 7, device=dev)
         fold_out = torch.empty(3, device=dev)
         params["plain"].grad = g_plain
+        params["b"].grad = g_b
         sources = {params["slabs"]: GradSource.slabs(part, stride, S),
-                   params["w"]: GradSource.lowrank(dy, out, x),
-                   params["b"]: GradSource.lowrank_bias(dy, out)}
+                   params["w"]: GradSource.slabs(w_part, w_stride, S)}
         opt.step_from_sources(sources, folds=[(fold_part, fold_out, 7, 4)])
-        # the same gradients, materialised (f64 products rounded to f32)
-        dym = (dy * (out > 0)).double()
+        # the same gradients, materialised
         ref_params["plain"].grad = g_plain
         ref_params["slabs"].grad = part.view(S, stride)[:, :n].sum(0).view(64, 33)
-        ref_params["w"].grad = (dym.t() @ x.double()).float()
-        ref_params["b"].grad = dym.sum(0).float()
+        ref_params["w"].grad = w_part.view(S, w_stride)[:, :F * K].sum(0).view(F, K)
+        ref_params["b"].grad = g_b
         ref.step()
         for k in params:
             a, b = params[k].detach(), ref_params[k].detach()
@@ -54,28 +53,6 @@ def test_step_from_sources_equals_torch_rmsprop(centered):
             assert float((sa - sb).abs().max()) <= 1e-5 * float(sb.abs().max()) + 1e-9, (it, k)
         want = fold_part.view(4, 7)[:, :3].sum(0)
         assert float((fold_out - want).abs().max()) <= 1e-6
-
-
-def test_lowrank_tile_layout_is_not_transposed():
-    """Asymmetric operands (guide: a symmetric B passes a row/col swap): W moves by exactly
-    lr * g / (sqrt(g^2 (1 - alpha)) + eps) with g = dy^T x known in closed form."""
-    from pfrl_amd.optimizers import FusedRMSprop, GradSource
-
-    dev = torch.device("cuda:0")
-    M, F, K = 4, 64, 128
-    w = torch.nn.Parameter(torch.zeros(F, K, device=dev))
-    dy = torch.zeros(M, F, device=dev)
-    x = torch.zeros(M, K, device=dev)
-    dy[0] = torch.arange(F, device=dev, dtype=torch.float32) + 1        # g[co][kk] = (co+1)(kk+1)
-    x[0] = torch.arange(K, device=dev, dtype=torch.float32) + 1
-    dy[2, 5] = 3.0
-    x[2, 77] = -2.0                                                      # + one off-grid term
-    opt = FusedRMSprop([w], lr=1.0, alpha=0.0, eps=1.0, centered=False)
-    opt.step_from_sources({w: GradSource.lowrank(dy, None, x)})
-    g = torch.outer(dy[0], x[0])
-    g[5, 77] += -6.0
-    want = -g / (g.abs() + 1.0)
-    assert torch.allclose(w.detach(), want, rtol=1e-6, atol=1e-7)
 
 
 def _run_updates(fused, n_updates=6, fwd_fold=True, extra_hidden=False):
@@ -158,22 +135,19 @@ def test_module_between_trunk_and_head_reads_the_folded_hidden_layer():
         np.testing.assert_array_equal(a, b)
 
 
-def test_optimizer_steps_riding_in_the_backward_launches_are_bit_identical():
+def test_hidden_layer_step_riding_in_the_last_backward_launch_is_bit_identical():
     """RMSprop steps as extra workgroups of the backward launches against the optimizer's own
     launch (same arithmetic on the same gradients / the same slab sums in the same order, so the
     same bits -- losses and every parameter after 6 updates):
       off    PFRL_RIDE_ALONG=0: every step in pfrl_rmsprop_fused_step
       last   round 5: the hidden layer's step in the first convolution's weight-gradient launch
-      all    round 6 (PFRL_RIDE_MORE=1; measured slower, not the default): + the head's in conv3's
-             backward launch, conv3's in conv2's, conv2's in conv1's (pfrl_ride_set); the
-             optimizer launch keeps conv1 + the loss fold
     and the rides are really taken."""
     from pfrl_amd import _native
     from pfrl_amd.nn import mfma_trunk
 
-    calls = {"ride": 0, "set": 0}
+    calls = {"ride": 0}
     lib = _native.lib()
-    real_ride, real_set = lib.pfrl_conv2d_nhwc_bwd_weight_ride, lib.pfrl_ride_set
+    real_ride = lib.pfrl_conv2d_nhwc_bwd_weight_ride
 
     class _Spy:
         def __getattr__(self, name):
@@ -182,14 +156,9 @@ def test_optimizer_steps_riding_in_the_backward_launches_are_bit_identical():
                     calls["ride"] += 1
                     return real_ride(*a)
                 return f
-            if name == "pfrl_ride_set":
-                def f(*a):
-                    calls["set"] += 1 if a[0] > 0 else 0
-                    return real_set(*a)
-                return f
             return getattr(lib, name)
 
-    old_lib, old_ride, old_more = _native.lib, mfma_trunk._RIDE, mfma_trunk._RIDE_MORE
+    old_lib, old_ride = _native.lib, mfma_trunk._RIDE
     _native.lib = lambda: _Spy()
     mfma_trunk._native.lib = _native.lib
     from pfrl_amd import optimizers
@@ -197,24 +166,22 @@ def test_optimizer_steps_riding_in_the_backward_launches_are_bit_identical():
     optimizers._native.lib = _native.lib
     out = {}
     try:
-        for name, ride, more in (("all", True, True), ("last", True, False), ("off", False, False)):
-            mfma_trunk._RIDE, mfma_trunk._RIDE_MORE = ride, more
-            calls["ride"] = calls["set"] = 0
+        for name, ride in (("last", True), ("off", False)):
+            mfma_trunk._RIDE = ride
+            calls["ride"] = 0
             p, l, used = _run_updates(True)
             out[name] = (p, l, used, dict(calls))
     finally:
         _native.lib = old_lib
         mfma_trunk._native.lib = old_lib
         optimizers._native.lib = old_lib
-        mfma_trunk._RIDE, mfma_trunk._RIDE_MORE = old_ride, old_more
+        mfma_trunk._RIDE = old_ride
     assert all(o[2] for o in out.values())
-    assert out["all"][3]["ride"] >= 1 and out["all"][3]["set"] >= 3 * out["all"][3]["ride"]
-    assert out["last"][3]["ride"] >= 1 and out["last"][3]["set"] == 0
-    assert out["off"][3] == {"ride": 0, "set": 0}
-    for name in ("last", "off"):
-        np.testing.assert_array_equal(out["all"][1], out[name][1])
-        for a, b in zip(out["all"][0], out[name][0]):
-            np.testing.assert_array_equal(a, b)
+    assert out["last"][3]["ride"] >= 1
+    assert out["off"][3] == {"ride": 0}
+    np.testing.assert_array_equal(out["last"][1], out["off"][1])
+    for a, b in zip(out["last"][0], out["off"][0]):
+        np.testing.assert_array_equal(a, b)
 
 
 @pytest.mark.parametrize("backend", ["nccl", "gloo"])

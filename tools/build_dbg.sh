@@ -1,5 +1,5 @@
 #!/bin/bash
-# Debug build of the HIP library with in-kernel phase clocks (tools/per_dbg.py, tools/qnet_phase.py):
+# Debug build of the HIP library with in-kernel phase clocks (tools/per_dbg2.py, tools/qnet_phase.py):
 #   bash tools/build_dbg.sh   ->  tools/libpfrl_amd_dbg.so
 set -e
 cd "$(dirname "$0")/.."

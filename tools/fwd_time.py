@@ -1,5 +1,5 @@
 """us per forward pass of the Nature trunk + head at B = 32 (HIP-graph replay of 10 passes), and
-fwd + bwd.  PFRL_FWD_EXPERIMENT=<bits> selects experimental tile programs (csrc/qnet.hip)."""
+fwd + bwd."""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,4 +19,4 @@ def fb():
     dut(xg).sum().backward()
 with torch.no_grad():
     print("max err fwd %.2e" % float((dut(xg).cpu() - ref(x)).abs().max()))
-print("exp=%s  fwd %.1f us   fwd+bwd %.1f us" % (os.environ.get("PFRL_FWD_EXPERIMENT", "0"), q.graph_time(fwd), q.graph_time(fb)))
+print("fwd %.1f us   fwd+bwd %.1f us" % (q.graph_time(fwd), q.graph_time(fb)))

@@ -31,8 +31,6 @@ PY
 }
 ARGS="--steps 6 --warmup 3 --num-envs 64 --capacity 100000 --no-cpu-baseline --no-also --no-data-path-only"
 PORT=29521 run bench_dqn_w2 X=1
-# a plan that takes the workers down (SIGSEGV in hipStreamEndCapture): the supervisors move on
-PORT=29531 run bench_dqn_w2_fork_crash PFRL_DP_FORK_IN_CAPTURE=1
 PORT=29522 run bench_dqn_w2_refused PFRL_RCCL_SHARED_DEVICE=0
 PORT=29523 run bench_dqn_w2_split PFRL_FORCE_SPLIT_GRAPH=1 PFRL_GRAPH_COLLECTIVE=0
 ARGS="--algo ppo --steps 128 --warmup 128 --num-envs 64 --no-cpu-baseline"

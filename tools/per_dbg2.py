@@ -1,9 +1,8 @@
-"""In-kernel phase timing of the PER sampler (debug build, tools/build_dbg.sh) on a tree in the
-state the Rainbow bench keeps it in: Python-float leaves (max_priority appends) with np.float32
-leaves where minibatches were drawn, np.float32 sums above them.
-    PFRL_TREE_SAMPLE=paths|lds python tools/per_dbg2.py [capacity]
-Phases (us per draw): paths: top rounds / fan-out / bottom round + siblings / repair / write-back
-                      lds:   top descent / fan-out / bottom descent / repair / write-back"""
+"""In-kernel phase timing of the PER sampler k_tree_sample_lean2 (debug build, tools/build_dbg.sh)
+on a tree in the state the Rainbow bench keeps it in: Python-float leaves (max_priority appends)
+with np.float32 leaves where minibatches were drawn, np.float32 sums above them.
+    python tools/per_dbg2.py [capacity]
+Phases (us, whole launch): prologue / draws / epilogue"""
 import ctypes, os, sys, time, numpy as np, torch
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root)
@@ -51,8 +50,8 @@ for B in (32, 32, 32, 32):
     torch.cuda.synchronize()
     dbg = (ctypes.c_ulonglong * 8)()
     L.pfrl_tree_debug_read(dbg)
-    t = np.array(list(dbg)[:5], dtype=np.float64) / (B if os.environ.get("PFRL_TREE_SAMPLE", "prefetch") != "prefetch" else B * B / B)
-    print(os.environ.get("PFRL_TREE_SAMPLE", "prefetch"), "per draw us (prefetch: whole-launch prologue / draws / epilogue):", (t / 100.0).round(2), "sum", (t.sum() / 100).round(2),
+    t = np.array(list(dbg)[:3], dtype=np.float64) / B
+    print("us, whole launch (prologue / draws / epilogue):", (t / 100.0).round(2), "sum", (t.sum() / 100).round(2),
           "| launch(es) by events %.1f us" % (ev0.elapsed_time(ev1) * 1e3), flush=True)
     err = torch.from_numpy((rs.rand(B) * 1.2).astype(np.float32)).to(dev)
     buf.update_errors_device(err, 0, 0.01 ** 0.5, 1, 1.01 ** 0.5, 0.01, 0.5)
