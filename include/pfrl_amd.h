@@ -370,6 +370,39 @@ int pfrl_ppo_head_loss(const float *h, const float *w_policy, const float *b_pol
                        float clip_eps_vf, float value_func_coef, float entropy_coef, float *dh,
                        float *dw_part, int32_t blocks, double *partial_ws, float *out4, void *stream);
 
+/* PPO with a diagonal Gaussian policy whose scale is shared by all rows
+ * (pfrl/policies/gaussian_policy.py:49-88 GaussianHeadWithStateIndependentCovariance, :97-124
+ * GaussianHeadWithFixedCovariance; examples/mujoco/reproduction/ppo/train_ppo.py:153-165).
+ * mean [N][A], scale [A] (a spherical variance expanded by the caller), 1 <= A <= 32.
+ * z != NULL (standard-normal draws [N][A]): out_action = fl(fl(z * scale) + mean), the two roundings
+ * of torch.normal(mean, std) = normal_(0, 1).mul_(std).add_(mean) (Normal.sample, the acting step of
+ * pfrl/agents/ppo.py:759-778), and out_entropy[N] = sum_j (0.5 + 0.5 log 2 pi + log scale_j)
+ * (may be NULL).  given_action != NULL ([N][A]): out_log_prob[N] = log pi(given_action | s) as
+ * Independent(Normal(mean, scale), 1).log_prob computes it (the value pass, ppo.py:110-142). */
+int pfrl_ppo_gaussian_act(const float *mean, const float *scale, const float *z,
+                          const float *given_action, float *out_action, float *out_entropy,
+                          float *out_log_prob, int32_t N, int32_t A, void *stream);
+/* PPO._lossfun (pfrl/agents/ppo.py:634-671) for that policy on mean [M][A], scale [A], value [M] and
+ * the minibatch columns, AND its gradient with respect to mean (dmean [M][A]), value (dvalue [M])
+ * and scale (dscale [A], NULL for a constant scale: row terms summed in f64, plus the entropy
+ * bonus's -entropy_coef / scale_j), in one launch + a one-workgroup finish.  clip_eps_vf < 0: no
+ * value clipping.  The surrogate / value-loss row arithmetic is pfrl_ppo_loss's (csrc/ppo_rows.h).
+ * out4 as pfrl_ppo_loss; partial_ws: (3 + A) * ceil(M / 256) doubles. */
+int pfrl_ppo_gaussian_loss(const float *mean, const float *scale, const float *value,
+                           const float *action, const float *adv, const float *log_prob_old,
+                           const float *v_pred_old, const float *v_teacher, int32_t M, int32_t A,
+                           float clip_eps, float clip_eps_vf, float value_func_coef,
+                           float entropy_coef, float *dmean, float *dvalue, float *dscale,
+                           double *partial_ws, float *out4, void *stream);
+/* pfrl_ppo_minibatch (pfrl/agents/ppo.py:483-511) for continuous actions: the action column holds
+ * A floats per dataset position, out_action [M][A]; everything else identical. */
+int pfrl_ppo_minibatch_f32act(int64_t M, const int64_t *idx, const float *adv, const float *mean_std,
+                              int standardize, const float *log_prob, const float *v_pred,
+                              const float *v_teacher, const float *action, int32_t A,
+                              const int32_t *state_refs, int32_t k, float *out_adv, float *out_logp,
+                              float *out_v, float *out_vt, float *out_action, int32_t *out_refs,
+                              void *stream);
+
 /* ------------------------------------------------------------------------
  * Optimizer step of the DQN update (pfrl/agents/dqn.py:360-365 calls
  * optimizer.step(); examples/atari/train_dqn_batch_ale.py:199-206 builds

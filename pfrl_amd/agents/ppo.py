@@ -222,7 +222,10 @@ class _ActGraph:
     from the eager path's (same distribution: tests/test_hip_kernels.py::
     test_ppo_act_head_matches_torch_categorical; ``PFRL_PPO_ACT_GRAPH=0`` or
     ``PFRL_PPO_ACT_HEAD=0`` restore the eager draws).  The reference's trajectory parity fixtures
-    (tests/golden/agent_trace_ppo.npz) are recorded with host envs and take the eager path."""
+    (tests/golden/agent_trace_ppo.npz) are recorded with host envs and take the eager path.
+    A Gaussian policy (``_gaussian_split``) keeps the eager path's action stream bit for bit: its
+    draws are ``torch.randn``'s, which is where ``Normal.sample`` starts, and
+    ``pfrl_ppo_gaussian_act`` applies ``torch.normal``'s two roundings."""
 
     def __init__(self, agent):
         self.agent = agent
@@ -269,10 +272,122 @@ class _ActGraph:
         self._split_cache = (model, out)
         return out
 
+    def _gaussian_split(self):
+        """(head-less model, head) when the policy branch ends in a Gaussian head whose scale does not
+        depend on the state -- ``GaussianHeadWithStateIndependentCovariance`` (spherical or diagonal,
+        any ``var_func``) or ``GaussianHeadWithFixedCovariance`` -- behind a ``Linear(., A)``,
+        A <= 32, in one of the two model shapes in use: the reference example's
+        ``Branched(Sequential(..., Linear(., A), head), value branch)``
+        (examples/mujoco/reproduction/ppo/train_ppo.py:153-189) or ``Sequential(body...,
+        Branched(Sequential(..., Linear(., A), head), value branch))``.  The head-less model is a
+        view built like ``_split``'s body (same classes, same children and parameters) that yields
+        ``(mean [M, A], value [M, 1])``; sampling, entropy, log-probability and the loss then run
+        as fused launches (csrc/ppo_gaussian.hip).  None for anything else -- a state-dependent
+        variance, recurrent models, non-f32 parameters, a subclassed or instance-patched
+        ``_lossfun`` / ``_sample_action`` -- which keeps torch.distributions + autograd."""
+        ag = self.agent
+        if (ag.recurrent or type(ag)._lossfun is not PPO._lossfun or "_lossfun" in ag.__dict__
+                or type(ag)._sample_action is not PPO._sample_action
+                or "_sample_action" in ag.__dict__):
+            return None
+        model = ag.model
+        hit = self.__dict__.get("_gaussian_cache")
+        if hit is not None and hit[0] is model:
+            return hit[1]
+        import collections
+
+        from pfrl_amd.nn import Branched
+        from pfrl_amd.policies import (GaussianHeadWithFixedCovariance,
+                                       GaussianHeadWithStateIndependentCovariance)
+
+        nn = torch.nn
+
+        def without_last(seq, replacement=None):
+            view = object.__new__(type(seq))
+            view.__dict__ = dict(seq.__dict__)
+            items = list(seq._modules.items())
+            last = [] if replacement is None else [(items[-1][0], replacement)]
+            view._modules = collections.OrderedDict(items[:-1] + last)
+            return view
+
+        def strip(branched):
+            """(Branched view whose policy branch ends at its Linear, head) or None."""
+            kids = list(branched.child_modules)
+            if len(kids) != 2 or type(kids[0]) is not nn.Sequential or len(kids[0]) < 2:
+                return None
+            pol, head = kids[0][len(kids[0]) - 2], kids[0][len(kids[0]) - 1]
+            if type(head) not in (GaussianHeadWithStateIndependentCovariance,
+                                  GaussianHeadWithFixedCovariance):
+                return None
+            if not (isinstance(pol, nn.Linear) and 1 <= pol.out_features <= ops.GAUSSIAN_MAX_A):
+                return None
+            view = object.__new__(type(branched))
+            view.__dict__ = dict(branched.__dict__)
+            view._modules = collections.OrderedDict(
+                child_modules=nn.ModuleList([without_last(kids[0]), kids[1]]))
+            return view, head, pol.out_features
+
+        out = None
+        found = None
+        if type(model) is Branched:
+            found = strip(model)
+            if found is not None:
+                out = (found[0], found[1])
+        elif (isinstance(model, nn.Sequential) and len(model) >= 2
+                and type(model[len(model) - 1]) is Branched):
+            found = strip(model[len(model) - 1])
+            if found is not None:
+                out = (without_last(model, replacement=found[0]), found[1])
+        if out is not None and not all(p.dtype == torch.float32 for p in model.parameters()):
+            out = None
+        if out is not None:
+            head, A = out[1], found[2]
+            if type(head) is GaussianHeadWithFixedCovariance:
+                # a constant: built once, outside any capture
+                const = torch.as_tensor(head.scale, dtype=torch.float32).to(ag.device)
+                if const.numel() not in (1, A) or bool((const <= 0).any()):
+                    out = None
+                else:
+                    self._fixed_scale = const.reshape(-1).expand(A).contiguous()
+            elif head.var_param.numel() not in (1, A):
+                out = None
+        self._gaussian_cache = (model, out)
+        return out
+
+    def gaussian_scale(self, head, A):
+        """The policy's scale vector [A]: ``sqrt(var_func(var_param))`` computed by torch, so that any
+        ``var_func`` works and its gradient is ``scale.backward(dscale)`` (a spherical variance
+        expands to A equal entries); the constant of a fixed-covariance head."""
+        from pfrl_amd.policies import GaussianHeadWithFixedCovariance
+
+        if type(head) is GaussianHeadWithFixedCovariance:
+            return self._fixed_scale
+        return torch.sqrt(head.var_func(head.var_param)).reshape(-1).expand(A)
+
+    def gaussian_act_split(self):
+        """``_gaussian_split()`` where the fused acting / value-pass launch applies
+        (``PFRL_PPO_ACT_HEAD=0``: torch.distributions, as for the categorical head)."""
+        if os.environ.get("PFRL_PPO_ACT_HEAD", "1") == "0" or self.agent.device.type != "cuda":
+            return None
+        return self._gaussian_split()
+
     def _body(self, refs, into=None):
         ag = self.agent
         b_state = ag._features(refs)
         split = self._split()
+        gauss = self.gaussian_act_split() if split is None else None
+        if gauss is not None:
+            # Gaussian policy: the draws are torch.randn's -- what Normal.sample's torch.normal
+            # starts from, at the generator offsets it would use -- scaled and shifted, with the
+            # entropy, in one launch: the action stream of the eager path bit for bit
+            assert into is None
+            view, head = gauss
+            with torch.no_grad(), evaluating(ag.model):
+                mean, value = view(b_state)
+                z = torch.randn(mean.shape, dtype=torch.float32, device=mean.device)
+                action, entropy = ops.ppo_gaussian_act(mean, self.gaussian_scale(head, mean.shape[1]),
+                                                       z=z)
+                return action, torch.stack([entropy, value.reshape(-1).float()])
         with torch.no_grad(), evaluating(ag.model):
             if split is not None:
                 body, pol, val = split
@@ -560,8 +675,25 @@ class PPO(agent.AttributeSavingMixin, agent.BatchAgent):
             return px       # (the trunk's first convolution applies phi itself)
         x = self._gather(refs_dev)
         if self.obs_normalizer is not None:
-            x = self.obs_normalizer(x, update=False)
+            x = self._normalize(x)
         return x
+
+    def _normalize(self, x):
+        """``obs_normalizer(x, update=False)``.  While a graph is being captured the statistics are
+        read IN PLACE: the module caches ``(var + eps) ** -0.5`` in a tensor that it drops whenever
+        the statistics learn, and a graph that had baked that tensor's address in would keep
+        normalising with the statistics of the rollout it was captured in.  Same expression, same
+        bits (nn/empirical_normalization.py ``forward``)."""
+        from pfrl_amd.nn import EmpiricalNormalization
+
+        n = self.obs_normalizer
+        if not (type(n) is EmpiricalNormalization and x.is_cuda
+                and torch.cuda.is_current_stream_capturing()):
+            return n(x, update=False)
+        y = (x - n._mean) * (n._var + n.eps) ** -0.5
+        if n.clip_threshold is not None:
+            y = torch.clamp(y, -n.clip_threshold, n.clip_threshold)
+        return y
 
     # -- acting --------------------------------------------------------------------
     def _sample_action(self, action_distrib):
@@ -590,6 +722,14 @@ class PPO(agent.AttributeSavingMixin, agent.BatchAgent):
             self._stats_at += 1
             action_dev, stats = self._act_graph.run_in_place(refs, ro.d_action, ring, ro.T, slot,
                                                              self._stage)
+            self.entropy_record.extend(stats[0])
+            self.value_record.extend(stats[1])
+        elif (self._act_graph.applicable() and self._act_graph.gaussian_act_split() is not None
+                and not (isinstance(batch_obs, DeviceObsBatch) and self.device_actions)):
+            # Gaussian policy, host env: gather, normaliser, network, draws and the fused head as
+            # one graph replay; the action goes to the host once, below
+            action_dev, stats = self._act_graph.run(refs_dev)
+            stats = stats.clone()
             self.entropy_record.extend(stats[0])
             self.value_record.extend(stats[1])
         elif (isinstance(batch_obs, DeviceObsBatch) and self.device_actions
@@ -732,10 +872,27 @@ class PPO(agent.AttributeSavingMixin, agent.BatchAgent):
         if self._act_graph is not None and self._act_graph.applicable() and (
                 actions_dev is None or actions_dev.dtype == torch.int64):
             split = self._act_graph._split()
+        gauss = None
+        if split is None and (actions_dev is None or (
+                actions_dev.dtype == torch.float32 and actions_dev.dim() == 2)):
+            if self._act_graph is None:
+                self._act_graph = _ActGraph(self)
+            gauss = self._act_graph.gaussian_act_split()
         with torch.no_grad(), evaluating(self.model):
             for lo in range(0, M, self.value_pass_chunk):
                 hi = min(M, lo + self.value_pass_chunk)
                 x = self._features(refs_dev[lo:hi])
+                if gauss is not None:
+                    # Gaussian policy: log pi(a | s) in one launch behind the head-less model,
+                    # written straight into the column
+                    view, head = gauss
+                    mean, vs = view(x)
+                    values[lo:hi] = vs.reshape(-1)
+                    if actions_dev is not None:
+                        ops.ppo_gaussian_act(mean, self._act_graph.gaussian_scale(head, mean.shape[1]),
+                                             given_action=actions_dev[lo:hi],
+                                             out_log_prob=log_probs[lo:hi])
+                    continue
                 if split is not None:
                     # heads + log pi(a | s) + V(s) in one launch behind the trunk (the acting path's
                     # kernel without the draw), written straight into the columns
@@ -880,13 +1037,17 @@ class PPO(agent.AttributeSavingMixin, agent.BatchAgent):
             # value pass and before the epochs (reference ppo.py:460-471)
             with torch.no_grad():
                 self.obs_normalizer.experience(self._gather(s_refs))
-        actions_i64 = actions if actions.dtype == torch.int64 else None
+        # the action column the device minibatch path takes: int64 [n], or float32 [n, A] of a
+        # Gaussian policy whose loss runs fused (_gaussian_loss_split)
+        gauss = (self._gaussian_loss_split() if actions.dtype == torch.float32 and actions.dim() == 2
+                 else None)
+        act_col = actions if actions.dtype == torch.int64 or gauss is not None else None
         self._last_dataset = dict(order=order, adv=adv, v_teacher=v_teacher, v_pred=v_pred,
                                   log_prob=log_probs, mean_std=mean_std)
 
-        captured = self._captured_update_ok(n, actions_i64)
+        captured = self._captured_update_ok(n, act_col)
         if captured:
-            cols = self._static_columns(adv, mean_std, log_probs, v_pred, v_teacher, actions_i64,
+            cols = self._static_columns(adv, mean_std, log_probs, v_pred, v_teacher, act_col,
                                         s_refs)
         for flat in minibatches:
             (idx,) = self._stage.upload([flat])
@@ -900,9 +1061,18 @@ class PPO(agent.AttributeSavingMixin, agent.BatchAgent):
                 self.policy_loss_record.extend(out["policy_loss"].clone())
                 self.n_updates += 1
                 continue
-            if actions_i64 is not None:
+            if gauss is not None:
+                # (capture off: the same fused step, on the rollout's own columns)
+                out = self._minibatch_step({"idx": idx}, dict(
+                    adv=adv, mean_std=mean_std, log_prob=log_probs, v_pred=v_pred,
+                    v_teacher=v_teacher, action=actions, s_refs=s_refs))
+                self.value_loss_record.extend(out["value_loss"])
+                self.policy_loss_record.extend(out["policy_loss"])
+                self.n_updates += 1
+                continue
+            if act_col is not None:
                 mb = ops.ppo_minibatch(idx, adv, mean_std, self.standardize_advantages, log_probs,
-                                       v_pred, v_teacher, actions_i64, s_refs)
+                                       v_pred, v_teacher, act_col, s_refs)
                 mb_actions = mb["action"]
             else:
                 dummy = torch.zeros(1, dtype=torch.int64, device=dev).expand(n).contiguous()
@@ -932,13 +1102,14 @@ class PPO(agent.AttributeSavingMixin, agent.BatchAgent):
     _update_graph = None
     _static_cols = None
 
-    def _captured_update_ok(self, n, actions_i64):
-        """Discrete actions, one process, a stock ``_lossfun``: the minibatch update is a fixed
-        launch sequence on fixed-size tensors and can be replayed from a HIP graph."""
+    def _captured_update_ok(self, n, act_col):
+        """Discrete actions (or the float action column of a Gaussian policy with the fused loss,
+        ``_gaussian_loss_split``), one process, a stock ``_lossfun``: the minibatch update is a
+        fixed launch sequence on fixed-size tensors and can be replayed from a HIP graph."""
         from pfrl_amd import distributed
 
         return (os.environ.get("PFRL_PPO_UPDATE_GRAPH", "1") != "0" and self.device.type == "cuda"
-                and actions_i64 is not None and self._dp_update_capturable()
+                and act_col is not None and self._dp_update_capturable()
                 and n % self.minibatch_size == 0
                 and type(self)._lossfun is PPO._lossfun and "_lossfun" not in self.__dict__)
 
@@ -973,11 +1144,11 @@ class PPO(agent.AttributeSavingMixin, agent.BatchAgent):
                 num(self.value_func_coef), num(self.max_grad_norm), bool(self.standardize_advantages),
                 id(self.model), tuple(id(m) for m in self.model.children()))
 
-    def _static_columns(self, adv, mean_std, log_probs, v_pred, v_teacher, actions_i64, s_refs):
+    def _static_columns(self, adv, mean_std, log_probs, v_pred, v_teacher, act_col, s_refs):
         """The rollout's columns in buffers that keep their addresses from rollout to rollout
         (what the captured update reads), refreshed with one copy each per rollout."""
         src = dict(adv=adv, mean_std=mean_std, log_prob=log_probs, v_pred=v_pred,
-                   v_teacher=v_teacher, action=actions_i64, s_refs=s_refs)
+                   v_teacher=v_teacher, action=act_col, s_refs=s_refs)
         cols = self._static_cols
         if cols is None or any(cols[k].shape != v.shape or cols[k].dtype != v.dtype
                                for k, v in src.items()):
@@ -1005,16 +1176,47 @@ class PPO(agent.AttributeSavingMixin, agent.BatchAgent):
             self._act_graph = _ActGraph(self)
         return self._act_graph._split()
 
-    def _minibatch_step(self, batch):
-        """reference ppo.py:480-532 for one minibatch, on the static columns."""
-        c = self._static_cols
+    def _gaussian_loss_split(self):
+        """(head-less model, head) when the loss of a minibatch can run as pfrl_ppo_gaussian_loss
+        (``_ActGraph._gaussian_split``); ``PFRL_PPO_FUSED_LOSS=0`` keeps torch.distributions +
+        autograd."""
+        if os.environ.get("PFRL_PPO_FUSED_LOSS", "1") == "0" or self.device.type != "cuda":
+            return None
+        if self._act_graph is None:
+            self._act_graph = _ActGraph(self)
+        return self._act_graph._gaussian_split()
+
+    def _minibatch_step(self, batch, cols=None):
+        """reference ppo.py:480-532 for one minibatch, on the static columns (``cols``: on these
+        columns instead -- the eager loop of a Gaussian policy)."""
+        c = self._static_cols if cols is None else cols
         with ops.profile_paused():
             mb = ops.ppo_minibatch(batch["idx"], c["adv"], c["mean_std"], self.standardize_advantages,
                                    c["log_prob"], c["v_pred"], c["v_teacher"], c["action"],
                                    c["s_refs"])
             states = self._features(mb["refs"])
         fused = self._fused_loss_split()
-        if fused is not None:
+        gauss = self._gaussian_loss_split() if mb["action"].dtype == torch.float32 else None
+        if gauss is not None:
+            # Gaussian policy: mean and value from the head-less model, the scale vector by torch
+            # (any var_func), then loss + its gradient with respect to all three in ONE launch
+            # (pfrl_ppo_gaussian_loss) instead of torch.distributions + autograd; backward starts
+            # at the three
+            view, head = gauss
+            mean, vs_pred = view(states)
+            scale = self._act_graph.gaussian_scale(head, mean.shape[1])
+            self.optimizer.zero_grad(set_to_none=True)
+            out4, dmean, dvalue, dscale = ops.ppo_gaussian_loss(
+                mean, scale, vs_pred, mb["action"], mb["adv"], mb["log_prob"], mb["v_pred"],
+                mb["v_teacher"], self.clip_eps, self.clip_eps_vf, self.value_func_coef,
+                self.entropy_coef, want_dscale=scale.requires_grad)
+            if scale.requires_grad:
+                torch.autograd.backward([mean, vs_pred, scale], [dmean, dvalue, dscale])
+            else:       # (a constant scale: dscale is dropped)
+                torch.autograd.backward([mean, vs_pred], [dmean, dvalue])
+            loss = out4[0]
+            records = {"value_loss": out4[2], "policy_loss": out4[1]}
+        elif fused is not None:
             # heads as plain layers on the trunk's output, then loss + its gradient with respect to
             # logits and values in ONE launch (pfrl_ppo_loss) instead of ~90 through
             # torch.distributions + autograd; backward starts at the logits / values

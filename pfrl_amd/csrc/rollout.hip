@@ -6,6 +6,7 @@
 #include <hip/hip_ext.h>
 
 #include "common.h"
+#include "ppo_rows.h"
 
 #include <stdlib.h>
 
@@ -427,19 +428,9 @@ __device__ __forceinline__ void ppo_loss_row(const float (&z)[A], float v, int a
         H -= p[j] > 0.f ? p[j] * lp[j] : 0.f;
         if (j == a) lpa = lp[j];
     }
-    const float ratio = expf(lpa - lpo);
-    const float lo = 1.0f - clip_eps, hi = 1.0f + clip_eps;
-    const float rc = fminf(fmaxf(ratio, lo), hi);
-    const float s1 = ratio * ad, s2 = rc * ad;
-    const float surr = fminf(s1, s2);
-    // d surr / d ratio: both operands of min carry it inside the clip range (a tie: half
-    // each, summing to adv); outside only the unclipped product does, if it is the minimum
-    const bool inside = ratio >= lo && ratio <= hi;
-    float ds = 0.f;
-    if (inside) ds = ad;
-    else if (s1 < s2) ds = ad;
-    else if (s1 == s2) ds = 0.5f * ad;
-    const float g_lpa = -inv_m * ds * ratio;
+    // (clipped surrogate and value loss: csrc/ppo_rows.h, shared with the Gaussian kernels)
+    float surr, g_lpa;
+    ppo_surrogate_row(lpa, lpo, ad, inv_m, clip_eps, surr, g_lpa);
     const float ge = ent_coef * inv_m;
 #pragma unroll
     for (int j = 0; j < A; ++j) {
@@ -448,23 +439,8 @@ __device__ __forceinline__ void ppo_loss_row(const float (&z)[A], float v, int a
         gj += p[j] > 0.f ? ge * p[j] * (lp[j] + H) : 0.f;
         g[j] = gj;
     }
-    const float d1 = v - vt;
-    float lv = d1 * d1, gv = 2.f * d1;
-    if (clip_eps_vf >= 0.f) {
-        const float vlo = vo - clip_eps_vf, vhi = vo + clip_eps_vf;
-        const float vc = fminf(fmaxf(v, vlo), vhi);
-        const float d2 = vc - vt;
-        const float l2 = d2 * d2;
-        // d vc / d v: torch.min(torch.max(v, lo), hi) -- 1 strictly inside, 1/2 at a bound
-        // (max / min split ties), 0 outside
-        float dvc = (v > vlo && v < vhi) ? 1.f : ((v == vlo || v == vhi) ? 0.5f : 0.f);
-        if (l2 > lv) {
-            lv = l2;
-            gv = 2.f * d2 * dvc;
-        } else if (l2 == lv) {
-            gv = 0.5f * (2.f * d1) + 0.5f * (2.f * d2 * dvc);
-        }
-    }
+    float lv, gv;
+    ppo_value_row(v, vo, vt, clip_eps_vf, lv, gv);
     gv_out = vf_coef * inv_m * gv;
     pol = -(double)surr;
     val = (double)lv;

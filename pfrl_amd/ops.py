@@ -589,23 +589,138 @@ def adv_stats(adv):
 
 def ppo_minibatch(idx, adv, mean_std, standardize, log_prob, v_pred, v_teacher, action,
                   state_refs):
+    """The columns of one minibatch (reference ppo.py:483-511).  ``action``: int64 [n] (discrete,
+    pfrl_ppo_minibatch) or float32 [n, A] (continuous, pfrl_ppo_minibatch_f32act)."""
     M = idx.numel()
     k = state_refs.shape[1]
     dev = adv.device
+    f32act = action.dtype == torch.float32
+    if f32act:
+        assert action.dim() == 2 and action.shape[1] >= 1, "float action column: [n, A]"
+    else:
+        assert action.dtype == torch.int64, "action column: int64 [n] or float32 [n, A]"
     out = dict(
         adv=torch.empty(M, dtype=torch.float32, device=dev),
         log_prob=torch.empty(M, dtype=torch.float32, device=dev),
         v_pred=torch.empty(M, dtype=torch.float32, device=dev),
         v_teacher=torch.empty(M, dtype=torch.float32, device=dev),
-        action=torch.empty(M, dtype=torch.int64, device=dev),
+        action=(torch.empty((M, action.shape[1]), dtype=torch.float32, device=dev) if f32act
+                else torch.empty(M, dtype=torch.int64, device=dev)),
         refs=torch.empty((M, k), dtype=torch.int32, device=dev),
     )
+    if f32act:
+        check(_native.lib().pfrl_ppo_minibatch_f32act(
+            M, _ptr(idx), _ptr(adv), _ptr(mean_std), int(standardize), _ptr(log_prob), _ptr(v_pred),
+            _ptr(v_teacher), _ptr(action), int(action.shape[1]), _ptr(state_refs), k,
+            _ptr(out["adv"]), _ptr(out["log_prob"]), _ptr(out["v_pred"]), _ptr(out["v_teacher"]),
+            _ptr(out["action"]), _ptr(out["refs"]), _stream()), "ppo_minibatch_f32act")
+        return out
     check(_native.lib().pfrl_ppo_minibatch(
         M, _ptr(idx), _ptr(adv), _ptr(mean_std), int(standardize), _ptr(log_prob), _ptr(v_pred),
         _ptr(v_teacher), _ptr(action), _ptr(state_refs), k, _ptr(out["adv"]),
         _ptr(out["log_prob"]), _ptr(out["v_pred"]), _ptr(out["v_teacher"]), _ptr(out["action"]),
         _ptr(out["refs"]), _stream()), "ppo_minibatch")
     return out
+
+
+GAUSSIAN_MAX_A = 32
+
+
+def _gaussian_args(mean, scale):
+    assert mean.dim() == 2 and mean.dtype == torch.float32 and scale.dtype == torch.float32
+    N, A = mean.shape
+    assert 1 <= A <= GAUSSIAN_MAX_A and scale.numel() == A, "scale: one value per action dimension"
+    return N, A, mean.detach().contiguous(), scale.detach().reshape(-1).contiguous()
+
+
+def ppo_gaussian_act(mean, scale, z=None, given_action=None, out_log_prob=None):
+    """``Independent(Normal(mean [N, A], scale [A]), 1)`` behind the network in one launch
+    (pfrl_ppo_gaussian_act).  ``z`` (standard-normal draws [N, A]): returns (action [N, A] =
+    z * scale + mean rounded as ``torch.normal`` rounds it, entropy [N]).  ``given_action`` [N, A]:
+    returns log pi(given_action | s) [N], written into ``out_log_prob`` if given."""
+    N, A, m, s = _gaussian_args(mean, scale)
+    dev = mean.device
+    assert (z is None) != (given_action is None), "either draws or recorded actions"
+    if z is not None:
+        assert z.dtype == torch.float32 and tuple(z.shape) == (N, A)
+        action = torch.empty((N, A), dtype=torch.float32, device=dev)
+        entropy = torch.empty(N, dtype=torch.float32, device=dev)
+        check(_native.lib().pfrl_ppo_gaussian_act(_ptr(m), _ptr(s), _ptr(z), None, _ptr(action),
+                                                  _ptr(entropy), None, N, A, _stream()),
+              "ppo_gaussian_act")
+        return action, entropy
+    assert given_action.dtype == torch.float32 and tuple(given_action.shape) == (N, A)
+    if out_log_prob is None:
+        out_log_prob = torch.empty(N, dtype=torch.float32, device=dev)
+    assert out_log_prob.dtype == torch.float32 and out_log_prob.numel() == N
+    check(_native.lib().pfrl_ppo_gaussian_act(_ptr(m), _ptr(s), None, _ptr(given_action), None, None,
+                                              _ptr(out_log_prob), N, A, _stream()),
+          "ppo_gaussian_act")
+    return out_log_prob
+
+
+def ppo_gaussian_loss(mean, scale, value, action, adv, log_prob_old, v_pred_old, v_teacher, clip_eps,
+                      clip_eps_vf, value_func_coef, entropy_coef, want_dscale=True):
+    """PPO._lossfun (reference pfrl/agents/ppo.py:634-671) for ``Independent(Normal(mean [M, A],
+    scale [A]), 1)`` and its gradient in one launch (pfrl_ppo_gaussian_loss).  Returns (out4 = [loss,
+    loss_policy, loss_value, mean entropy], dmean [M, A], dvalue shaped like ``value``, dscale shaped
+    like ``scale`` or None): the caller starts backward at mean / value / scale with these."""
+    M, A, m, s = _gaussian_args(mean, scale)
+    dev = mean.device
+    v = value.detach().reshape(-1).contiguous()
+    assert action.dtype == torch.float32 and tuple(action.shape) == (M, A) and v.numel() == M
+    dmean = torch.empty_like(m)
+    dvalue = torch.empty(M, dtype=torch.float32, device=dev)
+    dscale = torch.empty(A, dtype=torch.float32, device=dev) if want_dscale else None
+    ws = torch.empty((3 + A) * ((M + 255) // 256), dtype=torch.float64, device=dev)
+    out = torch.empty(4, dtype=torch.float32, device=dev)
+    check(_native.lib().pfrl_ppo_gaussian_loss(
+        _ptr(m), _ptr(s), _ptr(v), _ptr(action), _ptr(adv.reshape(-1)), _ptr(log_prob_old.reshape(-1)),
+        _ptr(v_pred_old.reshape(-1)) if clip_eps_vf is not None else None, _ptr(v_teacher.reshape(-1)),
+        M, A, float(clip_eps), -1.0 if clip_eps_vf is None else float(clip_eps_vf),
+        float(value_func_coef), float(entropy_coef), _ptr(dmean), _ptr(dvalue), _ptr(dscale), _ptr(ws),
+        _ptr(out), _stream()), "ppo_gaussian_loss")
+    return out, dmean, dvalue.view(value.shape), (dscale.view(scale.shape) if want_dscale else None)
+
+
+def gaussian_ppo_loss_closed_form(mean, scale, value, action, adv, log_prob_old, v_pred_old, v_teacher,
+                                  clip_eps, clip_eps_vf, value_func_coef, entropy_coef):
+    """What pfrl_ppo_gaussian_loss computes, restated with torch tensor operations in the tensors' own
+    dtype and device (float64 on the CPU in the tests): out4 and the closed-form gradients with
+    respect to mean [M, A], value [M] and scale [A], ties split as torch's min / max backward split
+    them.  No autograd; the kernel's maths pinned where no GPU exists."""
+    M, A = mean.shape
+    v = value.reshape(-1)
+    d = action - mean
+    log_s = scale.log()
+    lp = (-(d * d) / (2 * scale * scale) - log_s - 0.9189385332046727).sum(-1)
+    H = (1.4189385332046727 + log_s).sum()
+    ratio = torch.exp(lp - log_prob_old)
+    lo, hi = 1.0 - clip_eps, 1.0 + clip_eps
+    s1, s2 = ratio * adv, ratio.clamp(lo, hi) * adv
+    surr = torch.min(s1, s2)
+    inside = (ratio >= lo) & (ratio <= hi)
+    ds = torch.where(inside | (s1 < s2), adv, torch.where(s1 == s2, 0.5 * adv, torch.zeros_like(adv)))
+    g_lp = -ds * ratio / M
+    d1 = v - v_teacher
+    lv, gv = d1 * d1, 2 * d1
+    if clip_eps_vf is not None:
+        vlo, vhi = v_pred_old - clip_eps_vf, v_pred_old + clip_eps_vf
+        vc = torch.min(torch.max(v, vlo), vhi)
+        d2 = vc - v_teacher
+        l2 = d2 * d2
+        dvc = torch.where((v > vlo) & (v < vhi), torch.ones_like(v),
+                          torch.where((v == vlo) | (v == vhi), 0.5 * torch.ones_like(v),
+                                      torch.zeros_like(v)))
+        g2 = 2 * d2 * dvc
+        gv = torch.where(l2 > lv, g2, torch.where(l2 == lv, 0.5 * gv + 0.5 * g2, gv))
+        lv = torch.max(lv, l2)
+    pol, val = -surr.mean(), lv.mean()
+    out4 = torch.stack([pol + value_func_coef * val - entropy_coef * H, pol, val, H])
+    dmean = g_lp[:, None] * d / (scale * scale)
+    dvalue = (value_func_coef / M) * gv
+    dscale = (g_lp[:, None] * (d * d / scale ** 3 - 1 / scale)).sum(0) - entropy_coef / scale
+    return out4, dmean, dvalue.view(value.shape), dscale
 
 
 class _DQNTDLoss(torch.autograd.Function):
