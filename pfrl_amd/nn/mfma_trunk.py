@@ -237,13 +237,25 @@ _WGRAD_MAX_SPLITS = int(os.environ.get("PFRL_WGRAD_MAX_SPLITS", "4096"))
 _FUSE_BWD = os.environ.get("PFRL_FUSE_BWD", "1") != "0"
 
 
-def _fused_bwd_ok(N, H, W, C, ST):
+def _fused_bwd_ok(N, H, W, C, ST, taps=1):
     """Both gradients of a layer in one launch: only where the input-gradient kernel runs
-    one of its small tile programs (the rule of dgrad_program() in csrc/qnet.hip)."""
+    one of its small tile programs (the rule of dgrad_program() in csrc/qnet.hip).  ``taps``:
+    (R / ST) * (S / ST) of a convolution, 1 for a linear layer.  dgrad_program() also keeps a
+    layer with a column permutation (perm_p != 0) off the position-tiled programs; this rule has
+    no such argument because only the linear layer (taps = 1, ST = 1: never position-tiled)
+    passes one.  A convolution called with a permutation would need it here, or it is refused
+    fusion from 1 024 images up without need."""
     if not _FUSE_BWD:
         return False
     mc = N * (H // ST) * (W // ST)
     z = ST * ST
+    if N >= 1024 and C % 32 == 0:
+        # from 1 024 images up dgrad_program() tiles by input position whatever the workgroup count
+        # (programs 8 and 9): small maps stay below the counts tested next
+        if ST == 1 and taps > 1 and C % 64 == 0:
+            return False
+        if ST > 1 and 64 % C == 0 and (z * C) % 64 == 0:
+            return False
     if C % 32 == 0 and _ceil_div(mc, 64) * (C // 32) * z >= 1024:
         return False
     if C % 64 == 0 and _ceil_div(mc, 64) * (C // 64) * z >= 1024:
@@ -605,7 +617,8 @@ class _Trunk(torch.autograd.Function):
                 OPT_SOURCES[w.data_ptr()] = GradSource.slabs(part, stride, splits)
                 OPT_SOURCES[params[2 * i + 1].data_ptr()] = GradSource.slabs(pb, stride, splits)
                 grads[2 * i], grads[2 * i + 1] = None, None
-            if i > 0 and _fused_bwd_ok(N, sp.H, sp.W, sp.C, sp.ST):
+            if i > 0 and _fused_bwd_ok(N, sp.H, sp.W, sp.C, sp.ST,
+                                       (sp.R // sp.ST) * (sp.S // sp.ST)):
                 dx = torch.empty((N, sp.H, sp.W, sp.C), dtype=torch.float32, device=dev)
                 check(lib.pfrl_conv2d_nhwc_bwd(_p(dy), None, _p(w), _p(below), _p(below), _p(dx), _p(pw),
                                                _p(pb), st, st, N, sp.H, sp.W, sp.C, sp.Cout, sp.R, sp.S,
