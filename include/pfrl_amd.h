@@ -404,6 +404,47 @@ int pfrl_ppo_minibatch_f32act(int64_t M, const int64_t *idx, const float *adv, c
                               void *stream);
 
 /* ------------------------------------------------------------------------
+ * TRPO's policy update around the Fisher-vector product (pfrl/agents/trpo.py; the product itself
+ * stays autograd's double backward).  csrc/trpo.hip.  Every sum is an f64 sum in a fixed order: two
+ * calls on the same operands give the same bits.
+ * ------------------------------------------------------------------------ */
+/* TRPO._compute_gain (trpo.py:415-420) and mean KL(old || new) (trpo.py:560-562, :666-670:
+ * torch.distributions.kl_divergence of two diagonal Normals, summed over A) for
+ * Independent(Normal(mean [M][A], scale [A]), 1) against the old policy's mean_old [M][A],
+ * scale_old [A]: out3 = {gain, mean KL, mean entropy}.  log pi(action | s) is pfrl_ppo_gaussian_act's,
+ * bit for bit, so an unchanged policy has ratio exactly 1 and KL exactly 0.  dmean [M][A] and
+ * dscale [A], both or neither NULL: the gradient of the gain with respect to mean and scale (what
+ * torch.autograd.grad([gain], ...) of trpo.py:577 starts from).  One launch + a one-workgroup
+ * finish.  partial_ws: (2 + A) * ceil(M / 256) doubles. */
+int pfrl_trpo_gaussian_eval(const float *mean, const float *scale, const float *mean_old,
+                            const float *scale_old, const float *action, const float *adv,
+                            const float *log_prob_old, int32_t M, int32_t A, float entropy_coef,
+                            float *dmean, float *dscale, double *partial_ws, float *out3,
+                            void *stream);
+/* pfrl.utils.conjugate_gradient (pfrl/utils/conjugate_gradient.py:21-33) with every scalar in a
+ * device state block of four doubles {rr, pAp, step, done}, so that no iteration ends in a host
+ * read.  init: x = 0, r = p = b, rr = b.b, done = 0.  step(Ap): x += a p, r -= a Ap with a = rr / pAp;
+ * if ||r|| < tol, done = 1; otherwise p = r + (rr' / rr) p, rr = rr'.  Once done is set a step
+ * changes nothing: max_iter unconditional steps leave what the reference's early return leaves.
+ * Vectors of up to pfrl_cg_workgroup_reach() elements take ONE launch per step, longer ones four
+ * (partial sums that every workgroup folds identically).  partial_ws: 2 * ceil(n / 4096) doubles. */
+int pfrl_cg_workgroup_reach(void);
+int pfrl_cg_init(const float *b, float *x, float *r, float *p, double *state, double *partial_ws,
+                 int64_t n, void *stream);
+int pfrl_cg_step(float *x, float *r, float *p, const float *Ap, double *state, double *partial_ws,
+                 int64_t n, float tol, void *stream);
+/* full_step = sqrt(2 max_kl / (d.Fd + 1e-8)) d (trpo.py:596-598) with the scalar kept on the device;
+ * out_scale_dfd = {the scale, d.Fd}.  partial_ws: ceil(n / 4096) doubles. */
+int pfrl_trpo_scale_step(const float *d, const float *Fd, double max_kl, float *full_step,
+                         float *out_scale_dfd, double *partial_ws, int64_t n, void *stream);
+/* One trial of the line search (trpo.py:651-657) in one launch over up to 24 parameter tensors:
+ * params[t][i] = base[off_t + i] + step_size * full_step[off_t + i], off_t the running sum of numel,
+ * a multiply and an add, each rounded (never an fma): `flat_params + step_size * full_step` bit for
+ * bit.  step_size == 0 copies base (the restore of trpo.py:694-699). */
+int pfrl_params_axpy(int32_t n_tensors, float *const *params, const int64_t *numel, const float *base,
+                     const float *full_step, float step_size, void *stream);
+
+/* ------------------------------------------------------------------------
  * Optimizer step of the DQN update (pfrl/agents/dqn.py:360-365 calls
  * optimizer.step(); examples/atari/train_dqn_batch_ale.py:199-206 builds
  * torch.optim.RMSprop(alpha=0.95, eps=1e-2, centered=True)).  One fused

@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libpfrl_amd.so")
 # measurement hook (tools/build_variant.sh): another build of the same sources, e.g. other compiler
 # flags, loaded instead of the in-tree library.  Never set by the package, the tests or bench.py.
 _LIB_OVERRIDE = os.environ.get("PFRL_AMD_LIB")
-SOURCES = ["frames.hip", "replay.hip", "sumtree.hip", "rollout.hip", "optim.hip", "tdloss.hip", "bias_act.hip", "noisy.hip", "c51.hip", "dueling.hip", "qnet.hip", "actor.hip", "hostplan.hip", "philox.hip", "ppo_gaussian.hip"]
+SOURCES = ["frames.hip", "replay.hip", "sumtree.hip", "rollout.hip", "optim.hip", "tdloss.hip", "bias_act.hip", "noisy.hip", "c51.hip", "dueling.hip", "qnet.hip", "actor.hip", "hostplan.hip", "philox.hip", "ppo_gaussian.hip", "trpo.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     # the parity contract is one correctly rounded IEEE op per source op
@@ -51,6 +51,7 @@ def build(force=False, verbose=False):
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     deps = srcs + [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "powf_glibc.h"), os.path.join(CSRC, "rms_update.h"),
                    os.path.join(CSRC, "nhwc.h"), os.path.join(CSRC, "ppo_rows.h"),
+                   os.path.join(CSRC, "gaussian_rows.h"),
                    os.path.join(_HERE, "..", "include", "pfrl_amd.h"),
                    os.path.abspath(__file__)]      # (the compiler flags live in this file)
     if not force and os.path.exists(LIB_PATH):
@@ -187,6 +188,12 @@ EXPORTS = {
     "pfrl_ppo_gaussian_act": (ctypes.c_int, "pppppppiip"),
     "pfrl_ppo_gaussian_loss": (ctypes.c_int, "ppppppppiiffffpppppp"),
     "pfrl_ppo_minibatch_f32act": (ctypes.c_int, "qpppippppipippppppp"),
+    "pfrl_trpo_gaussian_eval": (ctypes.c_int, "pppppppiifppppp"),
+    "pfrl_cg_workgroup_reach": (ctypes.c_int, []),
+    "pfrl_cg_init": (ctypes.c_int, "ppppppqp"),
+    "pfrl_cg_step": (ctypes.c_int, "ppppppqfp"),
+    "pfrl_trpo_scale_step": (ctypes.c_int, "ppdpppqp"),
+    "pfrl_params_axpy": (ctypes.c_int, "ippppfp"),
     "pfrl_rmsprop_step": (ctypes.c_int, "ipppppffffip"),
     "pfrl_rmsprop_fused_step": (ctypes.c_int, "ipffffip"),
     "pfrl_dqn_td_loss": (ctypes.c_int, "ppppppppqiiippppp"),

@@ -535,40 +535,15 @@ class PPO(agent.AttributeSavingMixin, agent.BatchAgent):
         self.max_recurrent_sequence_len = max_recurrent_sequence_len
         self.act_deterministically = act_deterministically
         self.max_grad_norm = max_grad_norm
-        self.value_pass_chunk = value_pass_chunk
-        # False (default): V over states AND next_states, as the reference (ppo.py:119-133).  On
-        # the device path rows of the second pass that ARE rows of the first -- the next
-        # observation of (t, env) is the observation of (t + 1, env) unless an episode ended --
-        # are not evaluated twice where that is provably the same bits (_next_value_plan); the
-        # result is the full second pass bit for bit (tests/test_bench_path_parity.py).
-        # True (opt-in): the same shortcut WITHOUT the guarantee -- the remaining rows run as a
-        # small batch of their own (other tile programs: values equal to f32 rounding only).
-        self.reuse_next_values = bool(reuse_next_values)
-        self.next_value_pass = None    # what the last rollout's second pass did (for bench.py)
         self.logger = getLogger(__name__)
-
-        self.rollout = None
-        self._act_graph = None
-        self.device_actions = os.environ.get("PFRL_DEVICE_STEP", "1") != "0"
-        self._last_action_dev = None
-        self.ingest = None         # DeviceReplayStore used for host-observation ingestion
-        self.frames = None
-        self.batch_last_state = None
-        self.batch_last_action = None
-        self._last_refs = None
-
-        self.value_record = _DeviceRecord(value_stats_window)
-        self.entropy_record = _DeviceRecord(entropy_stats_window)
+        self._init_rollout_state(value_stats_window, entropy_stats_window, value_pass_chunk,
+                                 reuse_next_values,
+                                 device_actions=os.environ.get("PFRL_DEVICE_STEP", "1") != "0")
         self.value_loss_record = _DeviceRecord(value_loss_stats_window)
         self.policy_loss_record = _DeviceRecord(policy_loss_stats_window)
-        self.explained_variance = np.nan
-        self.n_updates = 0
-        self._reward_mode = None
         from pfrl_amd.distributed import GradientAllReducer
 
         self.grad_reducer = GradientAllReducer(self.model)
-        self._host = None
-        self._rec = None
         if on_gpu and not (recurrent and os.environ.get("PFRL_PPO_RECURRENT_HOST") == "1"):
             from pfrl_amd.staging import StagingRing
 
@@ -589,6 +564,40 @@ class PPO(agent.AttributeSavingMixin, agent.BatchAgent):
             from pfrl_amd.agents.ppo_host import HostRollouts
 
             self._host = HostRollouts(self)
+
+    def _init_rollout_state(self, value_stats_window, entropy_stats_window, value_pass_chunk,
+                            reuse_next_values, device_actions):
+        """Everything the rollout, acting and value-pass methods of this class read that is not a
+        constructor argument of the algorithm: one place, shared with the agents that reuse those
+        methods (agents/trpo.py)."""
+        self.value_pass_chunk = value_pass_chunk
+        # False (default): V over states AND next_states, as the reference (ppo.py:119-133).  On
+        # the device path rows of the second pass that ARE rows of the first -- the next
+        # observation of (t, env) is the observation of (t + 1, env) unless an episode ended --
+        # are not evaluated twice where that is provably the same bits (_next_value_plan); the
+        # result is the full second pass bit for bit (tests/test_bench_path_parity.py).
+        # True (opt-in): the same shortcut WITHOUT the guarantee -- the remaining rows run as a
+        # small batch of their own (other tile programs: values equal to f32 rounding only).
+        self.reuse_next_values = bool(reuse_next_values)
+        self.next_value_pass = None    # what the last rollout's second pass did (for bench.py)
+
+        self.rollout = None
+        self._act_graph = None
+        self.device_actions = device_actions
+        self._last_action_dev = None
+        self.ingest = None         # DeviceReplayStore used for host-observation ingestion
+        self.frames = None
+        self.batch_last_state = None
+        self.batch_last_action = None
+        self._last_refs = None
+
+        self.value_record = _DeviceRecord(value_stats_window)
+        self.entropy_record = _DeviceRecord(entropy_stats_window)
+        self.explained_variance = np.nan
+        self.n_updates = 0
+        self._reward_mode = None
+        self._host = None          # the list-of-dicts rollout, where the agent takes the host route
+        self._rec = None           # the recurrent device rollout
 
     @property
     def memory(self):

@@ -723,6 +723,130 @@ def gaussian_ppo_loss_closed_form(mean, scale, value, action, adv, log_prob_old,
     return out4, dmean, dvalue.view(value.shape), dscale
 
 
+# ---- TRPO's policy update around the Fisher-vector product (csrc/trpo.hip) ---------------------------
+def trpo_gaussian_eval(mean, scale, mean_old, scale_old, action, adv, log_prob_old, entropy_coef,
+                       want_grad=False):
+    """``TRPO._compute_gain`` (reference pfrl/agents/trpo.py:415-420) and mean KL(old || new) for
+    ``Independent(Normal(mean [M, A], scale [A]), 1)`` against the old policy's ``mean_old`` /
+    ``scale_old`` (pfrl_trpo_gaussian_eval).  Returns out3 = [gain, mean KL, mean entropy] on the device,
+    and with ``want_grad`` also (dmean [M, A], dscale shaped like ``scale``): the gradient of the gain."""
+    M, A, m, s = _gaussian_args(mean, scale)
+    _, _, mo, so = _gaussian_args(mean_old, scale_old)
+    dev = mean.device
+    assert tuple(mo.shape) == (M, A) and M >= 1
+    assert action.dtype == torch.float32 and tuple(action.shape) == (M, A)
+    assert adv.dtype == torch.float32 and adv.numel() == M
+    assert log_prob_old.dtype == torch.float32 and log_prob_old.numel() == M
+    dmean = torch.empty_like(m) if want_grad else None
+    dscale = torch.empty(A, dtype=torch.float32, device=dev) if want_grad else None
+    ws = torch.empty((2 + A) * ((M + 255) // 256), dtype=torch.float64, device=dev)
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    check(_native.lib().pfrl_trpo_gaussian_eval(
+        _ptr(m), _ptr(s), _ptr(mo), _ptr(so), _ptr(action), _ptr(adv.reshape(-1)),
+        _ptr(log_prob_old.reshape(-1)), M, A, float(entropy_coef), _ptr(dmean), _ptr(dscale), _ptr(ws),
+        _ptr(out), _stream()), "trpo_gaussian_eval")
+    if want_grad:
+        return out, dmean, dscale.view(scale.shape)
+    return out
+
+
+def trpo_gaussian_eval_closed_form(mean, scale, mean_old, scale_old, action, adv, log_prob_old,
+                                   entropy_coef):
+    """What pfrl_trpo_gaussian_eval computes, restated with torch tensor operations in the tensors' own
+    dtype (float64 on the CPU in the tests): out3 and the closed-form gradient of the gain with respect
+    to mean [M, A] and scale [A].  No autograd; the kernel's maths pinned where no GPU exists."""
+    M = mean.shape[0]
+    d = action - mean
+    log_s = scale.log()
+    lp = (-(d * d) / (2 * scale * scale) - log_s - 0.9189385332046727).sum(-1)
+    H = (1.4189385332046727 + log_s).sum()
+    term = torch.exp(lp - log_prob_old) * adv
+    t = (mean_old - mean) / scale
+    v = (scale_old / scale) ** 2
+    kl = (0.5 * t * t).sum(-1).mean() + (0.5 * (v - 1 - v.log())).sum()
+    out3 = torch.stack([term.mean() + entropy_coef * H, kl, H])
+    g = term / M
+    dmean = g[:, None] * d / (scale * scale)
+    dscale = (g[:, None] * (d * d / scale ** 3 - 1 / scale)).sum(0) + entropy_coef / scale
+    return out3, dmean, dscale
+
+
+def cg_workgroup_reach():
+    """Longest vector for which pfrl_cg_step is one launch."""
+    return int(_native.lib().pfrl_cg_workgroup_reach())
+
+
+class DeviceCG:
+    """``pfrl.utils.conjugate_gradient`` (reference pfrl/utils/conjugate_gradient.py) with x, r, p and
+    the scalars {rr, pAp, step, done} on the device (pfrl_cg_init / pfrl_cg_step): the caller supplies
+    ``A p`` for the current ``p`` and calls :meth:`step` ``max_iter`` times without reading anything
+    back -- after convergence a step changes nothing."""
+
+    def __init__(self, b, tol=1e-10):
+        assert b.is_cuda and b.dim() == 1 and b.dtype == torch.float32 and b.numel() >= 1
+        b = b.detach().contiguous()
+        self.n = b.numel()
+        self.tol = float(tol)
+        self.x, self.r, self.p = (torch.empty_like(b) for _ in range(3))
+        self.state = torch.empty(4, dtype=torch.float64, device=b.device)
+        self._ws = torch.empty(2 * ((self.n + 4095) // 4096), dtype=torch.float64, device=b.device)
+        check(_native.lib().pfrl_cg_init(_ptr(b), _ptr(self.x), _ptr(self.r), _ptr(self.p),
+                                         _ptr(self.state), _ptr(self._ws), self.n, _stream()), "cg_init")
+
+    def step(self, Ap):
+        assert Ap.is_cuda and Ap.dtype == torch.float32 and Ap.numel() == self.n
+        check(_native.lib().pfrl_cg_step(_ptr(self.x), _ptr(self.r), _ptr(self.p),
+                                         _ptr(Ap.detach().contiguous()), _ptr(self.state),
+                                         _ptr(self._ws), self.n, self.tol, _stream()), "cg_step")
+
+
+def conjugate_gradient_device(A_product_func, b, tol=1e-10, max_iter=10):
+    """The reference's ``conjugate_gradient(A_product_func, b, tol, max_iter)`` without a host read."""
+    cg = DeviceCG(b, tol)
+    for _ in range(max_iter):
+        cg.step(A_product_func(cg.p))
+    return cg.x
+
+
+def trpo_scale_step(d, Fd, max_kl):
+    """``sqrt(2 max_kl / (d . Fd + 1e-8)) * d`` (reference trpo.py:596-598) without a host read
+    (pfrl_trpo_scale_step).  Returns (full_step, [scale, d . Fd] on the device)."""
+    assert d.is_cuda and d.dtype == torch.float32 and d.dim() == 1 and Fd.shape == d.shape
+    assert Fd.dtype == torch.float32
+    n = d.numel()
+    full_step = torch.empty_like(d)
+    out = torch.empty(2, dtype=torch.float32, device=d.device)
+    ws = torch.empty((n + 4095) // 4096, dtype=torch.float64, device=d.device)
+    check(_native.lib().pfrl_trpo_scale_step(_ptr(d.detach().contiguous()), _ptr(Fd.detach().contiguous()),
+                                             float(max_kl), _ptr(full_step), _ptr(out), _ptr(ws), n,
+                                             _stream()), "trpo_scale_step")
+    return full_step, out
+
+
+def params_axpy(params, base, full_step, step_size):
+    """``param_i <- (base + step_size * full_step)[off_i : off_i + numel_i]`` for every tensor of
+    ``params`` (contiguous f32), bit for bit what the reference's split / reshape / ``copy_`` of
+    ``flat_params + step_size * full_step`` leaves (trpo.py:651-657) -- one launch per 24 tensors
+    (pfrl_params_axpy).  ``step_size = 0`` restores ``base``."""
+    params = [p.data if isinstance(p, torch.nn.Parameter) else p for p in params]
+    total = sum(p.numel() for p in params)
+    assert base.dtype == torch.float32 and full_step.dtype == torch.float32
+    assert base.numel() == total and full_step.numel() == total, "flat vectors cover all parameters"
+    assert all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in params)
+    base_ptr, step_ptr = _ptr(base).value, _ptr(full_step).value
+    off = 0
+    lib = _native.lib()
+    for lo in range(0, len(params), 24):
+        group = [p for p in params[lo:lo + 24]]
+        n = len(group)
+        P = (ctypes.c_void_p * n)(*[p.data_ptr() for p in group])
+        L = (ctypes.c_int64 * n)(*[p.numel() for p in group])
+        check(lib.pfrl_params_axpy(n, P, L, ctypes.c_void_p(base_ptr + 4 * off),
+                                   ctypes.c_void_p(step_ptr + 4 * off), float(step_size), _stream()),
+              "params_axpy")
+        off += sum(p.numel() for p in group)
+
+
 class _DQNTDLoss(torch.autograd.Function):
     """loss = sum/mean_b w_b L(Q(s)[a] - target); one HIP launch computes the loss,
     its gradient w.r.t. Q(s), the selected Q values and |TD error|."""
