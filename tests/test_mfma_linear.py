@@ -2,9 +2,11 @@
 
 CPU: `accelerate_mlp` leaves parameters, names, state_dict keys and CPU results untouched.
 GPU: forward and all three gradients against torch's own F.linear / relu in f32, through the
-C ABI (`pfrl_linear_fwd`, `pfrl_conv2d_nhwc_bwd*`), at the shapes of the SAC / TD3 example
-networks (in_features 376 and 376 + 17: not multiples of 32, rows not 16-byte aligned).
-Tolerance 2e-5 relative to the output scale: same f32 products, different summation order.
+module (`accelerate_mlp` / `_LinearSlot`, which call `pfrl_linear_fwd`, `pfrl_conv2d_nhwc_bwd*`),
+at the shapes of the SAC / TD3 example networks (in_features 376 and 376 + 17: not multiples of
+32, rows not 16-byte aligned).  Tolerance 2e-5 relative to the output scale: same f32 products,
+different summation order.  The C ABI itself is checked element by element against float64 in
+tests/test_linear_envelope.py.
 """
 import copy
 
