@@ -37,8 +37,12 @@ __device__ __forceinline__ void ppo_value_row(float v, float vo, float vt, float
         const float d2 = vc - vt;
         const float l2 = d2 * d2;
         // d vc / d v: torch.min(torch.max(v, lo), hi) -- 1 strictly inside, 1/2 at a bound
-        // (max / min split ties), 0 outside
-        float dvc = (v > vlo && v < vhi) ? 1.f : ((v == vlo || v == vhi) ? 0.5f : 0.f);
+        // (max / min split ties), 0 outside; the two factors multiply, so clip_eps_vf == 0 with
+        // v == v_old (lo == hi == v) is halved twice: 1/4
+        const float dmax = v > vlo ? 1.f : (v == vlo ? 0.5f : 0.f);
+        const float vm = fmaxf(v, vlo);
+        const float dmin = vm < vhi ? 1.f : (vm == vhi ? 0.5f : 0.f);
+        const float dvc = dmax * dmin;
         if (l2 > lv) {
             lv = l2;
             gv = 2.f * d2 * dvc;
