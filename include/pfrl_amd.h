@@ -563,6 +563,28 @@ int pfrl_c51_loss(const float *q_dist, const int64_t *action, const float *next_
                   float *out_q, float *out_delta, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Implicit Quantile Network (IQN) loss in one launch: replaces
+ *   pfrl/agents/iqn.py:176-255 compute_eltwise_huber_quantile_loss, compute_(weighted_)value_loss
+ *   pfrl/agents/iqn.py:340-400 _compute_target_values / _compute_y_and_taus / _compute_loss
+ *   pfrl/action_value.py QuantileDiscreteActionValue.greedy_actions / evaluate_actions_as_quantiles
+ * quantiles f32 [B][N][A] online net at taus [B][N]; next_quantiles f32 [B][N'][A] target net at
+ * taus'; next_select f32 [B][K][A] target net at taus~; 1 <= B <= 4096; 1 <= N, N', K, A <= 64.
+ *   g         = first argmax_a (sum_k next_select[b][k][a]) / K        (k increasing)
+ *   t[b][j]   = reward[b] + (discount[b] * (1 - terminal[b])) * next_quantiles[b][j][g]
+ *   y[i]      = quantiles[b][i][action[b]],  u = y[i] - t[j]
+ *   el[i][j]  = |taus[b][i] - (t[j] < y[i] ? 1 : 0)| * (|u| < 1 ? 0.5 u u : |u| - 0.5)
+ *   delta[b]  = sum_ij el / (N N')
+ *   loss      = sum_b c_b sum_i (sum_j el) / N',  c_b = (weights ? weights[b] : 1) (mean ? 1/B : 1)
+ *   out_grad [B][N][A] = d loss / d quantiles: c_b (sum_j w clamp(u, -1, 1)) / N' at action[b],
+ *                        +0.0 elsewhere;  out_t [B][N'] = t (may be NULL, like weights)
+ * One workgroup, no float atomics: the same inputs give the same bits on every run. */
+int pfrl_iqn_loss(const float *quantiles, const int64_t *action, const float *taus,
+                  const float *next_quantiles, const float *next_select, const float *reward,
+                  const float *discount, const float *terminal, const float *weights, int32_t B,
+                  int32_t N, int32_t Np, int32_t K, int32_t A, int32_t mean, float *out_loss,
+                  float *out_grad, float *out_delta, float *out_t, void *stream);
+
+/* ------------------------------------------------------------------------
  * Distributional dueling head (pfrl/q_functions/dueling_dqn.py:116-127), forward
  * and backward in one launch each.  ya f32 [B][A][Z] advantage logits, ys f32 [B][Z]
  * state-value logits, Z <= 64:

@@ -5,7 +5,11 @@ Mirrors ``pfrl.agents.iqn`` (/root/reference/pfrl/agents/iqn.py): cosine embeddi
 and its accumulation (:211-255), ``IQN`` (:258-433).  Replay, sampling, gathers and the
 captured update are DQN's; the quantile thresholds are drawn with ``torch.rand`` on
 the agent's device, three draws per update in the reference's order (taus for the
-prediction, taus~ for the greedy action, taus' for the target).
+prediction, taus~ for the greedy action, taus' for the target).  On the GPU everything behind
+the three network passes -- greedy action, Bellman target, the quantile Huber loss of every
+pair, its gradient and the priorities -- is one HIP launch (``pfrl_iqn_loss``); the
+stock-PyTorch composite is the CPU path and the path of subclasses that override the target
+or loss computation.
 """
 import math
 
@@ -144,13 +148,71 @@ class IQN(dqn.DQN):
         self._q_all = av.q_values.detach()
         return av.evaluate_actions_as_quantiles(exp_batch["action"]), taus
 
+    def _fused_iqn_applicable(self):
+        """``_compute_target_values`` / ``_compute_y_and_taus`` / ``_compute_loss`` are the
+        reference's extension points: a subclass that overrides any of them keeps the composite
+        path, on every device (the rule of ``CategoricalDQN._fused_c51_applicable``)."""
+        cls = type(self)
+        return (self.fused_td_loss and self.device.type == "cuda"
+                and cls._compute_target_values is IQN._compute_target_values
+                and cls._compute_y_and_taus is IQN._compute_y_and_taus
+                and cls._compute_loss is IQN._compute_loss)
+
+    def _compute_loss_fused_iqn(self, exp_batch, errors_out, want_errors, record):
+        """Same quantities as the composite path below with everything behind the three network
+        passes in ONE launch (pfrl_iqn_loss): greedy action, Bellman target, quantile Huber loss,
+        its gradient, the priorities.  The passes and the three threshold draws keep the
+        reference's order: online at taus, then target at taus~ and at taus'."""
+        from pfrl_amd import ops
+
+        batch_size = exp_batch["reward"].shape[0]
+        tau2av = self._action_value(self.model, exp_batch["state"],
+                                    exp_batch.get("recurrent_state"))
+        taus = self._rand(batch_size, self.quantile_thresholds_N)
+        av = tau2av(taus)
+        self._q_all = av.q_values.detach()
+        self._last_y = self._q_all.reshape(-1)
+        if record:
+            self.q_record.extend(self._last_y)
+        with torch.no_grad():
+            taus_tilde = self._rand(batch_size, self.quantile_thresholds_K)
+            target_next_tau2av = self._action_value(self.target_model, exp_batch["next_state"],
+                                                    exp_batch.get("next_recurrent_state"))
+            select = target_next_tau2av(taus_tilde)
+            taus_prime = self._rand(batch_size, self.quantile_thresholds_N_prime)
+            target_next = target_next_tau2av(taus_prime)
+        if not ops.iqn_loss_supported(av.quantiles, target_next.quantiles, select.quantiles):
+            # outside the launch's gate (more than 64 thresholds or actions, another dtype): the
+            # composite expression on the passes already made -- no draw is repeated
+            with torch.no_grad():
+                next_maxz = target_next.evaluate_actions_as_quantiles(select.greedy_actions)
+                t = (exp_batch["reward"].unsqueeze(-1) + exp_batch["discount"].unsqueeze(-1)
+                     * (1.0 - exp_batch["is_state_terminal"].unsqueeze(-1)) * next_maxz)
+            y = av.evaluate_actions_as_quantiles(exp_batch["action"])
+            return self._loss_of_pairs(y, t, taus, exp_batch, errors_out, want_errors)
+        loss, delta = ops.iqn_loss(
+            av.quantiles, exp_batch["action"], taus, target_next.quantiles, select.quantiles,
+            exp_batch["reward"], exp_batch["discount"], exp_batch["is_state_terminal"],
+            exp_batch.get("weights"), self.batch_accumulator == "mean")
+        self._analytic_backward = (av.quantiles, loss.grad_fn.saved_tensors[0]
+                                   if loss.grad_fn is not None else None)
+        if errors_out is not None:
+            del errors_out[:]
+            errors_out.extend(delta.cpu().numpy())
+        return loss, (delta if errors_out is not None or want_errors else None)
+
     def _compute_loss(self, exp_batch, errors_out=None, want_errors=False, record=True):
+        if self._fused_iqn_applicable():
+            return self._compute_loss_fused_iqn(exp_batch, errors_out, want_errors, record)
         y, taus = self._compute_y_and_taus(exp_batch)
         self._last_y = self._q_all.reshape(-1)
         if record:
             self.q_record.extend(self._last_y)
         with torch.no_grad():
             t = self._compute_target_values(exp_batch)
+        return self._loss_of_pairs(y, t, taus, exp_batch, errors_out, want_errors)
+
+    def _loss_of_pairs(self, y, t, taus, exp_batch, errors_out, want_errors):
         eltwise_loss = compute_eltwise_huber_quantile_loss(y, t, taus)
         delta = None
         if errors_out is not None or want_errors:

@@ -1166,6 +1166,52 @@ def c51_loss(q_dist, action, next_dist, next_select, z_values, reward, discount,
                           terminal, weights, mean)
 
 
+class _IQNLoss(torch.autograd.Function):
+    """IQN loss (greedy action, Bellman target, quantile Huber loss over every pair) in one HIP
+    launch; the same launch produces d loss / d quantiles and the per-sample priorities."""
+
+    @staticmethod
+    def forward(ctx, quantiles, action, taus, next_quantiles, next_select, reward, discount,
+                terminal, weights, mean):
+        B, N, A = quantiles.shape
+        Np, K = next_quantiles.shape[1], next_select.shape[1]
+        assert taus.shape == (B, N) and next_quantiles.shape == (B, Np, A)
+        assert next_select.shape == (B, K, A)
+        dev = quantiles.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        grad = torch.empty((B, N, A), dtype=torch.float32, device=dev)
+        delta = torch.empty(B, dtype=torch.float32, device=dev)
+        check(_native.lib().pfrl_iqn_loss(
+            _ptr(quantiles.detach().contiguous()), _ptr(action.contiguous()),
+            _ptr(taus.contiguous()), _ptr(next_quantiles.contiguous()),
+            _ptr(next_select.contiguous()), _ptr(reward), _ptr(discount), _ptr(terminal),
+            _ptr(weights.contiguous()) if weights is not None else None, B, N, Np, K, A,
+            int(mean), _ptr(loss), _ptr(grad), _ptr(delta), None, _stream()), "iqn_loss")
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(delta)
+        ctx.set_materialize_grads(False)
+        return loss.view(()), delta
+
+    @staticmethod
+    def backward(ctx, g_loss, g_delta):
+        (grad,) = ctx.saved_tensors
+        return (grad * g_loss,) + (None,) * 9
+
+
+def iqn_loss_supported(quantiles, next_quantiles, next_select):
+    ts = (quantiles, next_quantiles, next_select)
+    return (all(t.is_cuda and t.dtype == torch.float32 and t.ndim == 3 for t in ts)
+            and 1 <= quantiles.shape[0] <= 4096
+            and all(1 <= t.shape[1] <= 64 and 1 <= t.shape[2] <= 64 for t in ts))
+
+
+def iqn_loss(quantiles, action, taus, next_quantiles, next_select, reward, discount, terminal,
+             weights, mean):
+    """-> (loss scalar with grad, per-sample mean quantile Huber loss [B])"""
+    return _IQNLoss.apply(quantiles, action, taus, next_quantiles, next_select, reward, discount,
+                          terminal, weights, mean)
+
+
 class _DuelingSoftmax(torch.autograd.Function):
     """q = softmax_atoms(ya - mean_actions(ya) + ys) for the distributional dueling head."""
 
