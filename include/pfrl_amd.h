@@ -517,6 +517,36 @@ int pfrl_dqn_head_td_loss(const float *h, const float *w, const float *bias, con
                           int64_t h_stride, const float *h_bias, float *h_out, float *dh_masked,
                           float dh_scale, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Target and loss of the DQN variants whose target is an operator on the target network's
+ * values at s and s', in one launch: replaces
+ *   pfrl/agents/al.py, pal.py, double_pal.py  _compute_y_and_t
+ *   pfrl/agents/dpp.py:19-83,99-127           _l_operator, _compute_target_values, _compute_y_and_t
+ *   pfrl/agents/dqn.py                        compute_value_loss, compute_weighted_value_loss
+ *   pfrl/action_value.py:60-79                evaluate_actions, compute_advantage, compute_expectation
+ * q, target_cur, target_next (and next_online) f32 [B][A]; B >= 1, 1 <= A <= 64.
+ * op: 0 AL, 1 PAL, 2 DoublePAL (param = alpha, rounded to f32), 3 DPP, 4 DPPL (param = eta > 0),
+ * 5 DPPGreedy (param unused); next_online non-NULL exactly for op 2.  With a = action[b],
+ * coef = discount (1 - terminal), max / argmax the first maximum:
+ *   y    = q[b][a]
+ *   AL   t = (r + coef max target_next) + alpha (target_cur[a] - max target_cur)
+ *   PAL  t = (r + coef max target_next) + alpha max(target_cur[a] - max target_cur,
+ *                                                   target_next[a] - max target_next)
+ *   DoublePAL  as PAL with target_next[argmax next_online] in the first term
+ *   DPP* t = (target_cur[a] + (r + coef L(target_next))) - L(target_cur),  L(x) =
+ *        sum_a softmax(eta x)_a x_a (DPP), logsumexp(eta x) / eta (DPPL), max x (DPPGreedy);
+ *        max-subtracted, sums over increasing a
+ *   loss, out_grad_q (non-zero at a only, +0.0 elsewhere), out_y, out_abs_delta = |y - t| as
+ *   pfrl_dqn_td_loss; out_t [B] = t (may be NULL, like weights).
+ * One workgroup, no float atomics: the same inputs give the same bits on every run.  Anything
+ * outside the gate returns PFRL_ERR_ARG and writes nothing. */
+int pfrl_dqn_operator_td_loss(const float *q, const float *target_cur, const float *target_next,
+                              const float *next_online, const int64_t *action, const float *reward,
+                              const float *discount, const float *terminal, const float *weights,
+                              int64_t B, int32_t A, int32_t op, float param, int clip_delta,
+                              int mean, float *out_loss, float *out_grad_q, float *out_y,
+                              float *out_abs_delta, float *out_t, void *stream);
+
 /* Fused bias + ReLU of the conv trunk (pfrl/nn/atari_cnn.py:40-47: activation(
  * layer(h)) with conv bias) on row-major [rows][C] activations, i.e.
  * channels_last conv outputs flattened over N*H*W.  Forward: y = max(x + b[c], 0)

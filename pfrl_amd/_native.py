@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libpfrl_amd.so")
 # measurement hook (tools/build_variant.sh): another build of the same sources, e.g. other compiler
 # flags, loaded instead of the in-tree library.  Never set by the package, the tests or bench.py.
 _LIB_OVERRIDE = os.environ.get("PFRL_AMD_LIB")
-SOURCES = ["frames.hip", "replay.hip", "sumtree.hip", "rollout.hip", "optim.hip", "tdloss.hip", "bias_act.hip", "noisy.hip", "c51.hip", "iqn.hip", "dueling.hip", "qnet.hip", "actor.hip", "hostplan.hip", "philox.hip", "ppo_gaussian.hip", "trpo.hip"]
+SOURCES = ["frames.hip", "replay.hip", "sumtree.hip", "rollout.hip", "optim.hip", "tdloss.hip", "operator_td.hip", "bias_act.hip", "noisy.hip", "c51.hip", "iqn.hip", "dueling.hip", "qnet.hip", "actor.hip", "hostplan.hip", "philox.hip", "ppo_gaussian.hip", "trpo.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     # the parity contract is one correctly rounded IEEE op per source op
@@ -202,6 +202,7 @@ EXPORTS = {
     "pfrl_bias_relu_bwd": (ctypes.c_int, "ppppppqiiqp"),
     "pfrl_c51_loss": (ctypes.c_int, "pppppppppiiiippppp"),
     "pfrl_iqn_loss": (ctypes.c_int, "pppppppppiiiiiippppp"),
+    "pfrl_dqn_operator_td_loss": (ctypes.c_int, "pppppppppqiifiipppppp"),
     "pfrl_dueling_softmax_fwd": (ctypes.c_int, "pppqiip"),
     "pfrl_dueling_softmax_bwd": (ctypes.c_int, "ppppqiip"),
     "pfrl_noisy_weights_fwd": (ctypes.c_int, "pppppppqqp"),

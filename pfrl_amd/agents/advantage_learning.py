@@ -2,8 +2,12 @@
 target is shifted by ``alpha`` times the action gap under the target network.
 
 Mirrors ``pfrl.agents.al.AL`` (:7-79), ``pal.PAL`` (:7-80) and ``double_pal.DoublePAL``
-(:7-71).  Only the target changes; replay, gathers and the captured update are DQN's
-(these targets are not the plain TD target, so the composite torch loss is used).
+(:7-71).  Only the target changes; replay, gathers and the captured update are DQN's.  On the
+GPU everything behind the network passes -- the maxima, the action gaps, the target, the loss,
+its gradient and the TD errors -- is one HIP launch (``pfrl_dqn_operator_td_loss``,
+``DQN._compute_loss_fused_operator``); the stock-PyTorch composite below is the CPU path, the
+path of ``fused_td_loss=False`` and of subclasses that override an extension point
+(``_fused_td_loss_applicable`` stays False: these are not the plain TD target).
 """
 import torch
 
@@ -42,6 +46,24 @@ class AL(dqn.DQN):
             target = t_q + self.alpha * self._gap_term(cur_adv, next_adv)
         return batch_q, target
 
+    # the fused route (DQN._compute_loss_fused_operator) -----------------------------------
+    def _operator_td(self):
+        return next(c for c in _STOCK if isinstance(self, c)).__name__, self.alpha
+
+    def _operator_y_and_t(self, exp_batch, qout, target_qout, target_next_qout, next_qout):
+        n = exp_batch["reward"].shape[0]
+        actions = exp_batch["action"]
+        batch_q = qout.evaluate_actions(actions)
+        with torch.no_grad():
+            next_q = (target_next_qout.max if next_qout is None else
+                      target_next_qout.evaluate_actions(next_qout.greedy_actions)).reshape(n)
+            t_q = exp_batch["reward"] + exp_batch["discount"] * (
+                1.0 - exp_batch["is_state_terminal"]) * next_q
+            cur_adv = target_qout.compute_advantage(actions).reshape(n)
+            next_adv = target_next_qout.compute_advantage(actions).reshape(n)
+            target = t_q + self.alpha * self._gap_term(cur_adv, next_adv)
+        return batch_q, target
+
 
 class PAL(AL):
     """Persistent AL: the larger of the action gaps at s and at s'."""
@@ -58,3 +80,7 @@ class DoublePAL(PAL):
             next_qout = self._action_value(self.model, exp_batch["next_state"],
                                            exp_batch.get("next_recurrent_state"))
         return target_next_qout.evaluate_actions(next_qout.greedy_actions)
+
+
+_STOCK = (DoublePAL, PAL, AL)
+AL._operator_td_stock = _STOCK

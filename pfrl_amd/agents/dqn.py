@@ -581,12 +581,84 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
             errors_out.extend(delta.cpu().numpy())
         return loss, delta
 
+    # -- targets that are an operator on Q'(s) and Q'(s'): AL / PAL / DoublePAL, DPP / DPPL / DPPGreedy
+    _operator_td_names = ("_compute_y_and_t", "_compute_target_values", "_compute_loss",
+                          "_l_operator", "_next_q", "_gap_term")
+    _operator_td_stock = ()     # the stock classes of a family, most derived first
+
+    def _operator_td(self):
+        """(op name of ``ops.OPERATOR_TD_OPS``, alpha or eta) of a stock operator agent."""
+        raise NotImplementedError()
+
+    def _operator_y_and_t(self, exp_batch, qout, target_qout, target_next_qout, next_qout):
+        """The composite (y, t) from network passes already made."""
+        raise NotImplementedError()
+
+    def _fused_operator_loss_applicable(self):
+        """The fused launch (pfrl_dqn_operator_td_loss) computes the stock targets of the six
+        operator agents.  ``_operator_td_names`` are their extension points: a subclass that
+        overrides any of them keeps the composite path, on every device (the rule of
+        ``IQN._fused_iqn_applicable``)."""
+        cls = type(self)
+        stock = next((c for c in cls._operator_td_stock if issubclass(cls, c)), None)
+        return (stock is not None and self.fused_td_loss and self.device.type == "cuda"
+                and not self.recurrent
+                and all(getattr(cls, n, None) is getattr(stock, n, None)
+                        for n in self._operator_td_names))
+
+    def _compute_loss_fused_operator(self, exp_batch, errors_out, want_errors, record):
+        """The network passes of the composite path in its order -- online at s, target at s,
+        target at s' (the step-batched values when they are there) and, for DoublePAL, online
+        at s' in evaluation mode -- then ONE launch for everything behind them."""
+        from pfrl_amd import ops
+        from pfrl_amd.action_value import DiscreteActionValue
+
+        op, param = self._operator_td()
+        qout = self._action_value(self.model, exp_batch["state"], None)
+        with torch.no_grad():
+            target_qout = self._action_value(self.target_model, exp_batch["state"], None)
+            target_next_qout = self._target_next_action_value(exp_batch)
+            next_qout = None
+            if op == "DoublePAL":
+                with evaluating(self.model):
+                    next_qout = self._action_value(self.model, exp_batch["next_state"], None)
+        avs = [av for av in (qout, target_qout, target_next_qout, next_qout) if av is not None]
+        if not (all(type(av) is DiscreteActionValue for av in avs)
+                and ops.dqn_operator_td_loss_supported(*[av.q_values for av in avs],
+                                                       op=op, param=param)):
+            # outside the launch's gate (a distributional action value, more than 64 actions,
+            # another dtype): the composite expression on the passes already made
+            y, t = self._operator_y_and_t(exp_batch, qout, target_qout, target_next_qout,
+                                          next_qout)
+            return self._loss_of_y_and_t(y, t, exp_batch, errors_out, want_errors, record)
+        loss, y, delta = ops.dqn_operator_td_loss(
+            qout.q_values, target_qout.q_values, target_next_qout.q_values,
+            next_qout.q_values if next_qout is not None else None, exp_batch["action"],
+            exp_batch["reward"], exp_batch["discount"], exp_batch["is_state_terminal"],
+            exp_batch.get("weights"), ops.OPERATOR_TD_OPS[op], param, self.clip_delta,
+            self.batch_accumulator == "mean")
+        # d(loss)/dQ(s) came out of the same launch: backward may start at Q(s)
+        self._analytic_backward = (qout.q_values, loss.grad_fn.saved_tensors[0]
+                                   if loss.grad_fn is not None else None)
+        self._last_y = y
+        if record:
+            self.q_record.extend(y)
+        if errors_out is not None:
+            del errors_out[:]
+            errors_out.extend(delta.cpu().numpy())
+        return loss, delta
+
     def _compute_loss(self, exp_batch, errors_out=None, want_errors=False, record=True):
         """Returns (loss, |y - t| per sample or None).  ``errors_out`` keeps the
         reference's list-filling form for callers that use it directly."""
         if self._fused_td_loss_applicable():
             return self._compute_loss_fused(exp_batch, errors_out, record)
+        if self._fused_operator_loss_applicable():
+            return self._compute_loss_fused_operator(exp_batch, errors_out, want_errors, record)
         y, t = self._compute_y_and_t(exp_batch)
+        return self._loss_of_y_and_t(y, t, exp_batch, errors_out, want_errors, record)
+
+    def _loss_of_y_and_t(self, y, t, exp_batch, errors_out, want_errors, record):
         self._last_y = y.detach()
         if record:
             self.q_record.extend(y)

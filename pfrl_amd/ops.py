@@ -884,6 +884,67 @@ def dqn_td_loss(q, action, target_q, next_q_online, reward, discount, terminal, 
                             weights, clip_delta, mean)
 
 
+OPERATOR_TD_OPS = {"AL": 0, "PAL": 1, "DoublePAL": 2, "DPP": 3, "DPPL": 4, "DPPGreedy": 5}
+
+
+class _DQNOperatorTDLoss(torch.autograd.Function):
+    """Target and loss of AL / PAL / DoublePAL / DPP / DPPL / DPPGreedy in one HIP launch
+    (pfrl_dqn_operator_td_loss); the same launch computes the gradient w.r.t. Q(s), the
+    selected Q values and |TD error|."""
+
+    @staticmethod
+    def forward(ctx, q, target_cur, target_next, next_online, action, reward, discount, terminal,
+                weights, op, param, clip_delta, mean):
+        B, A = q.shape
+        assert target_cur.shape == (B, A) and target_next.shape == (B, A)
+        qc = q.detach().contiguous()
+        loss = torch.empty(1, dtype=torch.float32, device=q.device)
+        grad_q = torch.empty((B, A), dtype=torch.float32, device=q.device)
+        y = torch.empty(B, dtype=torch.float32, device=q.device)
+        delta = torch.empty(B, dtype=torch.float32, device=q.device)
+        check(_native.lib().pfrl_dqn_operator_td_loss(
+            _ptr(qc), _ptr(target_cur.contiguous()), _ptr(target_next.contiguous()),
+            _ptr(next_online.contiguous()) if next_online is not None else None,
+            _ptr(action.contiguous()), _ptr(reward), _ptr(discount), _ptr(terminal),
+            _ptr(weights.contiguous()) if weights is not None else None, B, A, int(op),
+            float(param), int(clip_delta), int(mean), _ptr(loss), _ptr(grad_q), _ptr(y),
+            _ptr(delta), None, _stream()), "dqn_operator_td_loss")
+        ctx.save_for_backward(grad_q)
+        ctx.mark_non_differentiable(y, delta)
+        ctx.set_materialize_grads(False)   # no zero-fill kernels for the unused outputs
+        return loss.view(()), y, delta
+
+    @staticmethod
+    def backward(ctx, g_loss, g_y, g_delta):
+        (grad_q,) = ctx.saved_tensors
+        return (grad_q * g_loss,) + (None,) * 12
+
+
+def dqn_operator_td_loss_supported(q, *others, op=None, param=None):
+    """float32 contiguous [B, A] matrices with A <= 64 on the GPU and, when given, an operator
+    (name or number) with a parameter the launch takes: inside the C gate."""
+    ts = (q,) + tuple(t for t in others if t is not None)
+    if op is not None:
+        op = OPERATOR_TD_OPS.get(op, op)
+        if op not in OPERATOR_TD_OPS.values():
+            return False
+        if param is not None:
+            with np.errstate(over="ignore"):
+                p32 = float(np.float32(param))                  # what the launch gets
+            if not np.isfinite(p32) or (op in (3, 4) and not p32 > 0.0):
+                return False
+    return (all(t.is_cuda and t.dtype == torch.float32 and t.ndim == 2
+                and tuple(t.shape) == tuple(q.shape) and t.is_contiguous() for t in ts)
+            and q.shape[0] >= 1 and 1 <= q.shape[1] <= 64)
+
+
+def dqn_operator_td_loss(q, target_cur, target_next, next_online, action, reward, discount,
+                         terminal, weights, op, param, clip_delta, mean):
+    """-> (loss scalar with grad, y [B], |y - t| [B]); ``op`` as in ``OPERATOR_TD_OPS``."""
+    return _DQNOperatorTDLoss.apply(q, target_cur, target_next, next_online, action, reward,
+                                    discount, terminal, weights, op, param, clip_delta, mean)
+
+
 class _DQNHeadTDLoss(torch.autograd.Function):
     """The narrow head ``q = h W^T + b``, the TD loss of ``_DQNTDLoss`` and the head's backward
     in one launch (pfrl_dqn_head_td_loss, a wave per row).  The sums over the batch (dL/dW,
