@@ -444,6 +444,26 @@ int pfrl_trpo_scale_step(const float *d, const float *Fd, double max_kl, float *
 int pfrl_params_axpy(int32_t n_tensors, float *const *params, const int64_t *numel, const float *base,
                      const float *full_step, float step_size, void *stream);
 
+/* REINFORCE (pfrl/agents/reinforce.py:176-195) on the M stored steps of a batch of episodes: per row
+ *   row = fl(fl(-ret) log pi(a | s)) - fl(beta H),   out2 = {sum(row) * inv_batchsize, mean H},
+ * AND the gradient of out2[0] with respect to the policy's last layer, in one launch + a
+ * one-workgroup finish (f64 sums per workgroup, folded in block order).  `ret` [M]: the returns the
+ * host computed, cast to f32; a NaN there reaches out2[0] and that row's gradient only.
+ * Categorical(logits [M][A]), action int64 [M], A <= 31:
+ *   dlogits_j = inv_batchsize (-ret (1[j = a] - p_j) + beta p_j (lp_j + H)).
+ * partial_ws: 2 * ceil(M / 256) doubles. */
+int pfrl_reinforce_loss(const float *logits, const int64_t *action, const float *ret, int32_t M,
+                        int32_t A, float inv_batchsize, float beta, float *dlogits,
+                        double *partial_ws, float *out2, void *stream);
+/* The same for Independent(Normal(mean [M][A], scale [A]), 1), action f32 [M][A], 1 <= A <= 32, with
+ * log pi and the entropy in pfrl_ppo_gaussian_act's order (csrc/gaussian_rows.h): dmean [M][A] and
+ * dscale [A] (NULL for a constant scale: row terms summed in f64, plus the entropy term's
+ * -beta M inv_batchsize / scale_j).  partial_ws: (2 + A) * ceil(M / 256) doubles. */
+int pfrl_reinforce_gaussian_loss(const float *mean, const float *scale, const float *action,
+                                 const float *ret, int32_t M, int32_t A, float inv_batchsize,
+                                 float beta, float *dmean, float *dscale, double *partial_ws,
+                                 float *out2, void *stream);
+
 /* ------------------------------------------------------------------------
  * Optimizer step of the DQN update (pfrl/agents/dqn.py:360-365 calls
  * optimizer.step(); examples/atari/train_dqn_batch_ale.py:199-206 builds

@@ -723,6 +723,82 @@ def gaussian_ppo_loss_closed_form(mean, scale, value, action, adv, log_prob_old,
     return out4, dmean, dvalue.view(value.shape), dscale
 
 
+# ---- REINFORCE's return-weighted policy loss (csrc/reinforce.hip) -----------------------------------
+REINFORCE_MAX_A = 31
+
+
+def _return_column(ret, M, dev):
+    assert ret.dtype == torch.float32 and ret.numel() == M and ret.device == dev, \
+        "returns: one float32 per row, on the logits' device"
+    return ret.reshape(-1).contiguous()
+
+
+def reinforce_loss(logits, action, ret, inv_batchsize, beta):
+    """REINFORCE's loss over the M stored steps of a batch of episodes (reference
+    pfrl/agents/reinforce.py:176-195) for ``Categorical(logits [M, A])``, A <= 31, and its gradient
+    with respect to the logits in one launch (pfrl_reinforce_loss).  ``ret`` [M]: the returns as
+    float32.  Returns (out2 = [sum(-R log pi - beta H) * inv_batchsize, mean entropy], dlogits
+    [M, A]); the caller starts backward at the logits with ``dlogits``."""
+    M, A = logits.shape
+    assert logits.dtype == torch.float32 and 1 <= A <= REINFORCE_MAX_A and M >= 1
+    assert action.dtype == torch.int64 and action.numel() == M
+    logits = logits.detach().contiguous()
+    dev = logits.device
+    dlogits = torch.empty_like(logits)
+    ws = torch.empty(2 * ((M + 255) // 256), dtype=torch.float64, device=dev)
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    check(_native.lib().pfrl_reinforce_loss(
+        _ptr(logits), _ptr(action.reshape(-1).contiguous()), _ptr(_return_column(ret, M, dev)), M, A,
+        float(inv_batchsize), float(beta), _ptr(dlogits), _ptr(ws), _ptr(out), _stream()),
+        "reinforce_loss")
+    return out, dlogits
+
+
+def reinforce_gaussian_loss(mean, scale, action, ret, inv_batchsize, beta, want_dscale=True):
+    """The same for ``Independent(Normal(mean [M, A], scale [A]), 1)``, A <= 32
+    (pfrl_reinforce_gaussian_loss).  Returns (out2, dmean [M, A], dscale shaped like ``scale`` or
+    None): the caller starts backward at mean / scale with these."""
+    M, A, m, s = _gaussian_args(mean, scale)
+    dev = mean.device
+    assert M >= 1 and action.dtype == torch.float32 and tuple(action.shape) == (M, A)
+    dmean = torch.empty_like(m)
+    dscale = torch.empty(A, dtype=torch.float32, device=dev) if want_dscale else None
+    ws = torch.empty((2 + A) * ((M + 255) // 256), dtype=torch.float64, device=dev)
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    check(_native.lib().pfrl_reinforce_gaussian_loss(
+        _ptr(m), _ptr(s), _ptr(action.contiguous()), _ptr(_return_column(ret, M, dev)), M, A,
+        float(inv_batchsize), float(beta), _ptr(dmean), _ptr(dscale), _ptr(ws), _ptr(out), _stream()),
+        "reinforce_gaussian_loss")
+    return out, dmean, (dscale.view(scale.shape) if want_dscale else None)
+
+
+def reinforce_loss_closed_form(logits, action, ret, inv_batchsize, beta):
+    """What pfrl_reinforce_loss computes, restated with torch tensor operations in the tensors' own
+    dtype and device (float64 on the CPU in the tests).  No autograd."""
+    lp = torch.log_softmax(logits, -1)
+    p = lp.exp()
+    H = -(p * lp).sum(-1)
+    onehot = torch.nn.functional.one_hot(action, logits.shape[1]).to(logits.dtype)
+    lpa = (lp * onehot).sum(-1)
+    out2 = torch.stack([(-ret * lpa - beta * H).sum() * inv_batchsize, H.mean()])
+    dlogits = inv_batchsize * (-ret[:, None] * (onehot - p) + beta * p * (lp + H[:, None]))
+    return out2, dlogits
+
+
+def reinforce_gaussian_loss_closed_form(mean, scale, action, ret, inv_batchsize, beta):
+    """What pfrl_reinforce_gaussian_loss computes, restated likewise."""
+    M = mean.shape[0]
+    d = action - mean
+    log_s = scale.log()
+    lp = (-(d * d) / (2 * scale * scale) - log_s - 0.9189385332046727).sum(-1)
+    H = (1.4189385332046727 + log_s).sum()
+    out2 = torch.stack([(-ret * lp - beta * H).sum() * inv_batchsize, H])
+    g = -ret * inv_batchsize
+    dmean = g[:, None] * d / (scale * scale)
+    dscale = (g[:, None] * (d * d / scale ** 3 - 1 / scale)).sum(0) - beta * M * inv_batchsize / scale
+    return out2, dmean, dscale
+
+
 # ---- TRPO's policy update around the Fisher-vector product (csrc/trpo.hip) ---------------------------
 def trpo_gaussian_eval(mean, scale, mean_old, scale_old, action, adv, log_prob_old, entropy_coef,
                        want_grad=False):
