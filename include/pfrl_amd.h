@@ -464,6 +464,38 @@ int pfrl_reinforce_gaussian_loss(const float *mean, const float *scale, const fl
                                  float beta, float *dmean, float *dscale, double *partial_ws,
                                  float *out2, void *stream);
 
+/* A2C.update (pfrl/agents/a2c.py:169-213) on the M = T N stored steps, row m = t N + e: with
+ * adv = fl(ret - value), ret [M] = returns[:-1] and value [M] the fresh value head output,
+ *   out3 = {value_loss = mean adv^2, action_loss = -mean(adv log pi(a | s)), entropy = mean H}
+ * in the order of A2C._last_losses, AND the gradient of
+ *   v_coef value_loss + pi_coef action_loss - ent_coef entropy
+ * (adv a constant in the action loss: advantages.detach()) with respect to the policy's last layer
+ * and the value column, in one launch + a one-workgroup finish (f64 sums per workgroup, folded in
+ * block order: two calls on the same operands give the same bits):
+ *   dvalue_m = v_coef 2 (value_m - ret_m) / M.
+ * avg [3] (may be NULL): the moving statistics in the order of A2C._avg {actor, value, entropy},
+ * advanced in place by the float32 sequence of a2c.py:197-213 on the float32 out3 just written,
+ *   avg_i = avg_i + fl(fl(1 - decay_i) fl(x_i - avg_i)).
+ * Categorical(logits [M][A]), 1 <= A <= 31; action f32 [M] holding the integer action as A2C.actions
+ * stores it -- it enters only through the comparison j == (int)action, a value outside [0, A)
+ * matches no j and indexes nothing:
+ *   dlogits_j = (1 / M) (-pi_coef adv (1[j = a] - p_j) + ent_coef p_j (lp_j + H)).
+ * partial_ws: 3 * ceil(M / 256) doubles. */
+int pfrl_a2c_loss(const float *logits, const float *value, const float *action, const float *ret,
+                  int32_t M, int32_t A, float pi_coef, float v_coef, float ent_coef, float *dlogits,
+                  float *dvalue, double *partial_ws, float *out3, float *avg, float decay_actor,
+                  float decay_value, float decay_entropy, void *stream);
+/* The same for Independent(Normal(mean [M][A], scale [A]), 1), action f32 [M][A], 1 <= A <= 32, with
+ * log pi and the entropy in pfrl_ppo_gaussian_act's order (csrc/gaussian_rows.h):
+ *   dmean_mj = (-pi_coef adv_m / M) (a_j - mu_j) / s_j^2,
+ *   dscale_j = sum_m (-pi_coef adv_m / M) (d^2 / s_j^3 - 1 / s_j) - ent_coef / s_j  (f64, cast once;
+ * NULL for a constant scale).  partial_ws: (3 + A) * ceil(M / 256) doubles. */
+int pfrl_a2c_gaussian_loss(const float *mean, const float *scale, const float *value,
+                           const float *action, const float *ret, int32_t M, int32_t A,
+                           float pi_coef, float v_coef, float ent_coef, float *dmean, float *dvalue,
+                           float *dscale, double *partial_ws, float *out3, float *avg,
+                           float decay_actor, float decay_value, float decay_entropy, void *stream);
+
 /* ------------------------------------------------------------------------
  * Optimizer step of the DQN update (pfrl/agents/dqn.py:360-365 calls
  * optimizer.step(); examples/atari/train_dqn_batch_ale.py:199-206 builds

@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libpfrl_amd.so")
 # measurement hook (tools/build_variant.sh): another build of the same sources, e.g. other compiler
 # flags, loaded instead of the in-tree library.  Never set by the package, the tests or bench.py.
 _LIB_OVERRIDE = os.environ.get("PFRL_AMD_LIB")
-SOURCES = ["frames.hip", "replay.hip", "sumtree.hip", "rollout.hip", "optim.hip", "tdloss.hip", "operator_td.hip", "bias_act.hip", "noisy.hip", "c51.hip", "iqn.hip", "dueling.hip", "qnet.hip", "actor.hip", "hostplan.hip", "philox.hip", "ppo_gaussian.hip", "trpo.hip", "reinforce.hip"]
+SOURCES = ["frames.hip", "replay.hip", "sumtree.hip", "rollout.hip", "optim.hip", "tdloss.hip", "operator_td.hip", "bias_act.hip", "noisy.hip", "c51.hip", "iqn.hip", "dueling.hip", "qnet.hip", "actor.hip", "hostplan.hip", "philox.hip", "ppo_gaussian.hip", "trpo.hip", "reinforce.hip", "a2c.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     # the parity contract is one correctly rounded IEEE op per source op
@@ -196,6 +196,8 @@ EXPORTS = {
     "pfrl_params_axpy": (ctypes.c_int, "ippppfp"),
     "pfrl_reinforce_loss": (ctypes.c_int, "pppiiffpppp"),
     "pfrl_reinforce_gaussian_loss": (ctypes.c_int, "ppppiiffppppp"),
+    "pfrl_a2c_loss": (ctypes.c_int, "ppppiifffpppppfffp"),
+    "pfrl_a2c_gaussian_loss": (ctypes.c_int, "pppppiifffppppppfffp"),
     "pfrl_rmsprop_step": (ctypes.c_int, "ipppppffffip"),
     "pfrl_rmsprop_fused_step": (ctypes.c_int, "ipffffip"),
     "pfrl_dqn_td_loss": (ctypes.c_int, "ppppppppqiiippppp"),

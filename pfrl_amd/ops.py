@@ -799,6 +799,115 @@ def reinforce_gaussian_loss_closed_form(mean, scale, action, ret, inv_batchsize,
     return out2, dmean, dscale
 
 
+# ---- A2C's actor-critic loss (csrc/a2c.hip) -----------------------------------------------------------
+A2C_MAX_A = 31
+
+
+def a2c_loss_supported(kind, head_out, value, action, ret):
+    """Do the operands of one A2C update fit ``a2c_loss`` (``kind`` "softmax": logits [M, A <= 31],
+    action [M]) or ``a2c_gaussian_loss`` ("gaussian": mean [M, A <= 32], action [M, A])?  float32
+    throughout, contiguous, on one GPU, one value and one return per row.  A subset of what the
+    entry points admit; whatever it refuses takes the agent's torch expression."""
+    if kind not in ("softmax", "gaussian") or head_out.dim() != 2:
+        return False
+    M, A = head_out.shape
+    if M < 1 or not 1 <= A <= (A2C_MAX_A if kind == "softmax" else GAUSSIAN_MAX_A):
+        return False
+    if value.numel() != M or ret.numel() != M or action.numel() != (M if kind == "softmax" else M * A):
+        return False
+    return all(t.is_cuda and t.device == head_out.device and t.dtype == torch.float32
+               and t.is_contiguous() for t in (head_out, value, action, ret))
+
+
+def _a2c_stats(avg, decay, dev):
+    if avg is None:
+        return None, (0.0, 0.0, 0.0)
+    assert avg.dtype == torch.float32 and avg.numel() == 3 and avg.device == dev and len(decay) == 3
+    return avg, tuple(float(d) for d in decay)
+
+
+def a2c_loss(logits, value, action, ret, pi_coef, v_coef, ent_coef, avg=None, decay=None):
+    """The three loss terms of one A2C update (reference pfrl/agents/a2c.py:169-213) for
+    ``Categorical(logits [M, A])``, A <= 31, and the gradient of ``v_coef value_loss + pi_coef
+    action_loss - ent_coef entropy`` with respect to the logits and the value column in one launch
+    (pfrl_a2c_loss).  ``action`` [M]: float32 holding the integer actions, as ``A2C.actions`` stores
+    them; ``ret`` [M]: ``returns[:-1]``.  ``avg`` [3] with ``decay`` (three floats), both in the order
+    of ``A2C._avg``: the moving statistics, advanced in place by the same launch.  Returns (out3 =
+    [value_loss, action_loss, entropy], dlogits [M, A], dvalue shaped like ``value``)."""
+    M, A = logits.shape
+    assert logits.dtype == torch.float32 and 1 <= A <= A2C_MAX_A and M >= 1
+    assert value.dtype == torch.float32 and value.numel() == M
+    assert action.dtype == torch.float32 and action.numel() == M
+    logits = logits.detach().contiguous()
+    v = value.detach().reshape(-1).contiguous()
+    dev = logits.device
+    avg, decay = _a2c_stats(avg, decay, dev)
+    dlogits = torch.empty_like(logits)
+    dvalue = torch.empty_like(v)
+    ws = torch.empty(3 * ((M + 255) // 256), dtype=torch.float64, device=dev)
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    check(_native.lib().pfrl_a2c_loss(
+        _ptr(logits), _ptr(v), _ptr(action.reshape(-1).contiguous()), _ptr(_return_column(ret, M, dev)),
+        M, A, float(pi_coef), float(v_coef), float(ent_coef), _ptr(dlogits), _ptr(dvalue), _ptr(ws),
+        _ptr(out), _ptr(avg), decay[0], decay[1], decay[2], _stream()), "a2c_loss")
+    return out, dlogits, dvalue.view(value.shape)
+
+
+def a2c_gaussian_loss(mean, scale, value, action, ret, pi_coef, v_coef, ent_coef, avg=None, decay=None,
+                      want_dscale=True):
+    """The same for ``Independent(Normal(mean [M, A], scale [A]), 1)``, A <= 32
+    (pfrl_a2c_gaussian_loss).  Returns (out3, dmean [M, A], dvalue shaped like ``value``, dscale
+    shaped like ``scale`` or None)."""
+    M, A, m, s = _gaussian_args(mean, scale)
+    dev = mean.device
+    assert M >= 1 and action.dtype == torch.float32 and tuple(action.shape) == (M, A)
+    assert value.dtype == torch.float32 and value.numel() == M
+    v = value.detach().reshape(-1).contiguous()
+    avg, decay = _a2c_stats(avg, decay, dev)
+    dmean = torch.empty_like(m)
+    dvalue = torch.empty_like(v)
+    dscale = torch.empty(A, dtype=torch.float32, device=dev) if want_dscale else None
+    ws = torch.empty((3 + A) * ((M + 255) // 256), dtype=torch.float64, device=dev)
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    check(_native.lib().pfrl_a2c_gaussian_loss(
+        _ptr(m), _ptr(s), _ptr(v), _ptr(action.contiguous()), _ptr(_return_column(ret, M, dev)), M, A,
+        float(pi_coef), float(v_coef), float(ent_coef), _ptr(dmean), _ptr(dvalue), _ptr(dscale),
+        _ptr(ws), _ptr(out), _ptr(avg), decay[0], decay[1], decay[2], _stream()), "a2c_gaussian_loss")
+    return out, dmean, dvalue.view(value.shape), (dscale.view(scale.shape) if want_dscale else None)
+
+
+def a2c_loss_closed_form(logits, value, action, ret, pi_coef, v_coef, ent_coef):
+    """What pfrl_a2c_loss computes, restated with torch tensor operations in the tensors' own dtype
+    and device (float64 on the CPU in the tests).  ``action``: integers in any dtype.  No autograd."""
+    M, A = logits.shape
+    lp = torch.log_softmax(logits, -1)
+    p = lp.exp()
+    H = -(p * lp).sum(-1)
+    onehot = torch.nn.functional.one_hot(action.long(), A).to(logits.dtype)
+    lpa = (lp * onehot).sum(-1)
+    adv = ret - value
+    out3 = torch.stack([(adv * adv).mean(), -(adv * lpa).mean(), H.mean()])
+    dlogits = (-pi_coef * adv[:, None] * (onehot - p) + ent_coef * p * (lp + H[:, None])) / M
+    dvalue = v_coef * 2 * (value - ret) / M
+    return out3, dlogits, dvalue
+
+
+def a2c_gaussian_loss_closed_form(mean, scale, value, action, ret, pi_coef, v_coef, ent_coef):
+    """What pfrl_a2c_gaussian_loss computes, restated likewise."""
+    M = mean.shape[0]
+    d = action - mean
+    log_s = scale.log()
+    lp = (-(d * d) / (2 * scale * scale) - log_s - 0.9189385332046727).sum(-1)
+    H = (1.4189385332046727 + log_s).sum()
+    adv = ret - value
+    out3 = torch.stack([(adv * adv).mean(), -(adv * lp).mean(), H])
+    g = -pi_coef * adv / M
+    dmean = g[:, None] * d / (scale * scale)
+    dvalue = v_coef * 2 * (value - ret) / M
+    dscale = (g[:, None] * (d * d / scale ** 3 - 1 / scale)).sum(0) - ent_coef / scale
+    return out3, dmean, dvalue, dscale
+
+
 # ---- TRPO's policy update around the Fisher-vector product (csrc/trpo.hip) ---------------------------
 def trpo_gaussian_eval(mean, scale, mean_old, scale_old, action, adv, log_prob_old, entropy_coef,
                        want_grad=False):

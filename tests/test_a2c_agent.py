@@ -1,0 +1,394 @@
+"""A2C with the fused loss launch (``fused_loss=True``, the default on a GPU) against the torch
+expression it replaces (``fused_loss=False``: the code as it stood) and against the reference:
+
+* categorical, teacher-forced on ``teacher_forced_a2c.npz`` through the setup of
+  tests/test_teacher_forced_loss.py (``_check_a2c``, which asserts losses / returns at 1e-5 and the
+  parameters after the step at 1e-5 / 1e-6), with ``agents.A2C`` replaced by a factory that fixes
+  ``fused_loss``, keeps the agents and records the gradient of every update before clipping;
+* categorical, the rollout of ``agent_trace_a2c_gae{0,1}.npz`` with the recorded actions replayed, both
+  routes side by side;
+* Gaussian, teacher-forced on ``teacher_forced_a2c_gaussian.npz`` (make_a2c_gaussian_fixture.py).
+
+A recording proxy in front of the library counts the calls of the two loss entry points.
+
+The gradient condition (COVERAGE row a27's): for every parameter tensor, with ref the gradient of a
+float64 CPU replica of the update (the same float32 parameters, inputs, actions and returns; the
+reference's expression under autograd),
+    max |fused - ref|  <=  max(4 max |composite - ref|, 8 u max |ref|),   u = 2^-24:
+the fused route may not be worse than four times the torch expression's own float32 error, with a floor
+of a few ulps of the largest entry where that error happens to be tiny.
+"""
+import copy
+import os
+import tempfile
+
+import numpy as np
+import pytest
+import torch
+
+from pfrl_amd import _native
+from test_teacher_forced_loss import GOLDEN, TOL, _check_a2c, _load_flat
+
+gpu = pytest.mark.gpu
+U = 2.0 ** -24
+LOSS_ENTRY_POINTS = ("pfrl_a2c_loss", "pfrl_a2c_gaussian_loss")
+
+
+class _RecordingLib:
+    """Stands in front of the loaded library: every ``pfrl_*`` entry point fetched through it is
+    counted when called."""
+
+    def __init__(self, lib):
+        self._lib = lib
+        self.calls = []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("pfrl_"):
+            return fn
+
+        def counted(*a):
+            self.calls.append(name)
+            return fn(*a)
+
+        return counted
+
+    def count(self, name):
+        return sum(1 for c in self.calls if c == name)
+
+
+@pytest.fixture
+def recorder(monkeypatch):
+    if not _native.available():
+        _native.build()
+    rec = _RecordingLib(_native.lib())
+    monkeypatch.setattr(_native, "_lib", rec)
+    return rec
+
+
+def _replica_grads(ag):
+    """The update's gradient from a float64 CPU copy of the model, on what the agent holds right after
+    its backward: the reference's expression (pfrl/agents/a2c.py:175-187) under autograd."""
+    T, N = ag.update_steps, ag.num_processes
+    model = copy.deepcopy(ag.model).cpu().double()
+    for p in model.parameters():
+        p.grad = None
+    x = ag._gather(ag.refs[:-1].reshape((T * N,) + tuple(ag.refs.shape[2:]))).detach().cpu().double()
+    pout, values = model(x)
+    actions = ag.actions.reshape(-1, *ag.action_shape).cpu().double()
+    advantages = ag.returns[:-1].cpu().double() - values.reshape((T, N))
+    value_loss = (advantages * advantages).mean()
+    action_loss = -(advantages.detach() * pout.log_prob(actions).reshape((T, N))).mean()
+    (value_loss * ag.v_loss_coef + action_loss * ag.pi_loss_coef
+     - pout.entropy().mean() * ag.entropy_coeff).backward()
+    return [p.grad.clone() for p in model.parameters()]
+
+
+def _watch(ag, seen):
+    """``grad_reducer.all_reduce`` runs right after backward and before clipping on both routes: record
+    the float32 gradient there, next to the float64 replica's."""
+    orig = ag.grad_reducer.all_reduce
+
+    def all_reduce():
+        orig()
+        got = [p.grad.detach().cpu().double() for p in ag.model.parameters()]
+        seen.append((got, _replica_grads(ag)))
+
+    ag.grad_reducer.all_reduce = all_reduce
+    return ag
+
+
+def _factory(monkeypatch, state):
+    """``agents.A2C`` -> a factory that passes ``state["fused_loss"]`` on, appends every agent it makes
+    to ``state["made"]`` and what ``_watch`` records to ``state["seen"]``."""
+    from pfrl_amd import agents
+
+    real = agents.A2C
+
+    def make(*a, **k):
+        ag = _watch(real(*a, fused_loss=state["fused_loss"], **k), state["seen"])
+        state["made"].append(ag)
+        return ag
+
+    monkeypatch.setattr(agents, "A2C", make)
+
+
+def _errors(seen):
+    """per update, per parameter: (max |got - ref|, max |ref|)"""
+    return [[(float((g - r).abs().max()), float(r.abs().max())) for g, r in zip(got, ref)]
+            for got, ref in seen]
+
+
+def _assert_gradient_condition(name, fused, composite):
+    assert len(fused) == len(composite) and len(fused) > 0
+    worst = (0.0, 0.0)
+    for k, (fu, co) in enumerate(zip(fused, composite)):
+        for i, ((ef, mag), (ec, _)) in enumerate(zip(fu, co)):
+            print("%s update %d parameter %d: fused error %.3e composite error %.3e max|ref| %.3e" % (
+                name, k, i, ef, ec, mag))
+            worst = (max(worst[0], ef / mag if mag else 0.0), max(worst[1], ec / mag if mag else 0.0))
+            assert ef <= max(4 * ec, 8 * U * mag), (name, k, i, ef, ec, mag)
+    print("%s worst relative gradient error: fused %.3e composite %.3e" % ((name,) + worst))
+
+
+# ================================================================== categorical, teacher-forced
+@gpu
+def test_teacher_forced_categorical_update_on_both_routes(monkeypatch, recorder):
+    runs, state = {}, {}
+    _factory(monkeypatch, state)
+    for fused in (True, False):
+        made, seen = [], []
+        state.update(fused_loss=fused, made=made, seen=seen)
+        before = recorder.count("pfrl_a2c_loss")
+        _check_a2c(0)                                   # (asserts 1e-5 / 1e-6 against the fixture)
+        calls = recorder.count("pfrl_a2c_loss") - before
+        assert len(made) == 5 and len(seen) == 5
+        assert calls == (5 if fused else 0), "one loss launch per update on the fused route, none off it"
+        assert all((ag._head_split() is not None) == fused for ag in made)
+        runs[fused] = (made, _errors(seen))
+    assert recorder.count("pfrl_a2c_gaussian_loss") == 0
+    for a, b in zip(runs[True][0], runs[False][0]):
+        sa, sb = a.get_statistics(), b.get_statistics()
+        assert [n for n, _ in sa] == [n for n, _ in sb] == ["average_actor", "average_value", "average_entropy"]
+        np.testing.assert_allclose([v for _, v in sa], [v for _, v in sb], rtol=TOL, atol=TOL)
+        assert all(t.dim() == 0 and t.device == a.device and not t.requires_grad for t in a._last_losses)
+    _assert_gradient_condition("categorical", runs[True][1], runs[False][1])
+
+
+def test_host_route_never_reaches_the_loss_launch(monkeypatch, recorder):
+    made = []
+    _factory(monkeypatch, {"fused_loss": True, "made": made, "seen": []})
+    _check_a2c(-1)
+    assert len(made) == 5 and all(ag._head_split() is None for ag in made)
+    assert not [c for c in recorder.calls if c in LOSS_ENTRY_POINTS]
+
+
+def _categorical_agent(n_actions, fused, seed=5):
+    import pfrl_amd as pfrl
+    from pfrl_amd import agents
+    from pfrl_amd.policies import SoftmaxCategoricalHead
+
+    T, N = 5, 4
+    torch.manual_seed(seed)
+    model = torch.nn.Sequential(
+        torch.nn.Flatten(), torch.nn.Linear(4 * 144, 32), torch.nn.ReLU(),
+        pfrl.nn.Branched(torch.nn.Sequential(torch.nn.Linear(32, n_actions), SoftmaxCategoricalHead()),
+                         torch.nn.Linear(32, 1)))
+    ag = agents.A2C(model, torch.optim.SGD(model.parameters(), lr=1e-2), gamma=0.99, num_processes=N,
+                    gpu=0, update_steps=T, max_grad_norm=0.5, fused_loss=fused)
+    g = torch.Generator().manual_seed(seed + 1)
+    table = torch.rand((T + 1) * N, 4, 12, 12, generator=g).to(ag.device)
+    actions = torch.randint(0, n_actions, (T, N), generator=g)
+    ag._flush_storage(N, 1, actions[0])
+    ag.refs = torch.arange((T + 1) * N, dtype=torch.int32, device=ag.device).view(T + 1, N, 1)
+    ag._gather = lambda refs, _t=table: _t[refs.reshape(-1).long()]
+    ag.actions = actions.float().to(ag.device)
+    ag.rewards = torch.randn(T, N, generator=g).to(ag.device)
+    ag.masks = (torch.rand(T, N, generator=g) > 0.1).float().to(ag.device)
+    ag.value_preds = torch.randn(T + 1, N, generator=g).to(ag.device)
+    return ag
+
+
+def _flat(ag):
+    return np.concatenate([p.detach().cpu().numpy().ravel() for p in ag.model.parameters()])
+
+
+@gpu
+def test_a_model_above_the_gate_takes_the_composite_route(recorder):
+    """32 actions: the split refuses the model, no loss launch is seen and the numbers are the
+    composite route's, bit for bit; 31 actions are admitted."""
+    got = []
+    for fused in (True, False):
+        ag = _categorical_agent(32, fused)
+        assert ag._head_split() is None
+        ag.update()
+        got.append((_flat(ag), [float(v) for v in ag._last_losses], ag.get_statistics()))
+    assert not [c for c in recorder.calls if c in LOSS_ENTRY_POINTS]
+    assert np.array_equal(got[0][0], got[1][0]) and got[0][1] == got[1][1] and got[0][2] == got[1][2]
+    ag = _categorical_agent(31, True)
+    assert ag._head_split() is not None and ag._head_split()[0] == "softmax"
+    ag.update()
+    assert recorder.count("pfrl_a2c_loss") == 1
+
+
+@gpu
+def test_other_models_parameters_and_subclasses_keep_the_torch_expression(recorder):
+    from pfrl_amd import agents
+
+    ag = _categorical_agent(6, True)
+    ag.model.double()
+    ag._split = None
+    assert ag._head_split() is None                         # (non-float32 parameters)
+
+    class Mine(agents.A2C):
+        def update(self):
+            return agents.A2C.update(self)
+
+    ag = _categorical_agent(6, True)
+    ag.__class__ = Mine
+    assert ag._head_split() is None
+    ag.update()
+    assert not [c for c in recorder.calls if c in LOSS_ENTRY_POINTS]
+
+
+# ================================================================== categorical, the recorded rollout
+def _drive_trace(use_gae, fused):
+    """The setup of tests/test_agent_parity.py::test_a2c_device_rollout_matches_reference."""
+    import pfrl_amd as pfrl
+    from pfrl_amd import agents
+    from pfrl_amd.envs.synthetic import HostSyntheticAtariVectorEnv
+    from pfrl_amd.nn import Branched
+    from pfrl_amd.policies import SoftmaxCategoricalHead
+
+    g = np.load(os.path.join(GOLDEN, "agent_trace_a2c_gae%d.npz" % int(use_gae)))
+    N = 4
+    pfrl.utils.set_random_seed(0)
+    env = HostSyntheticAtariVectorEnv(N, seed=7, frame_shape=(12, 12), p_done=0.08)
+
+    def phi(x):
+        return np.asarray(x, dtype=np.float32) / 255
+
+    torch.manual_seed(4321)
+    model = torch.nn.Sequential(
+        torch.nn.Flatten(), torch.nn.Linear(4 * 144, 32), torch.nn.ReLU(),
+        Branched(torch.nn.Sequential(torch.nn.Linear(32, 6), SoftmaxCategoricalHead()),
+                 torch.nn.Linear(32, 1)))
+    opt = torch.optim.SGD(model.parameters(), lr=1e-2)
+    ag = agents.A2C(model, opt, gamma=0.99, num_processes=N, gpu=0, update_steps=5, phi=phi,
+                    use_gae=use_gae, tau=0.95, max_grad_norm=0.5, fused_loss=fused)
+    step = [0]
+
+    def replay_action(pout):
+        a = torch.as_tensor(g["actions"][step[0]], device=ag.device)
+        step[0] += 1
+        return a
+
+    ag._sample_action = replay_action
+    losses, orig = [], ag.update
+
+    def spy():
+        orig()
+        losses.append([float(v) for v in ag._last_losses])
+
+    ag.update = spy
+    pfrl.experiments.train_agent_batch(ag, env, 120, tempfile.mkdtemp())
+    return np.asarray(losses), np.asarray([v for _, v in ag.get_statistics()]), g
+
+
+@gpu
+@pytest.mark.parametrize("use_gae", [True, False])
+def test_recorded_rollout_gives_the_same_losses_and_statistics_on_both_routes(use_gae, recorder):
+    la, sa, g = _drive_trace(use_gae, True)
+    n = recorder.count("pfrl_a2c_loss")
+    lb, sb, _ = _drive_trace(use_gae, False)
+    assert la.shape == lb.shape == (len(g["returns"]), 3)
+    assert n == len(la) and recorder.count("pfrl_a2c_loss") == n
+    print("largest loss difference between the routes", np.abs(la - lb).max())
+    np.testing.assert_allclose(la, lb, rtol=TOL, atol=TOL)
+    np.testing.assert_allclose(sa, sb, rtol=TOL, atol=TOL)
+    np.testing.assert_allclose(sa, g["stats"], rtol=1e-3, atol=1e-6)
+
+
+# ================================================================== Gaussian, teacher-forced
+OBS, A, T, N = 8, 3, 5, 4
+
+
+def _gaussian_agent(use_gae, gpu_id, fused):
+    """The model and agent of tests/golden/make_a2c_gaussian_fixture.py."""
+    import pfrl_amd as pfrl
+    from pfrl_amd import agents
+    from pfrl_amd.policies import GaussianHeadWithStateIndependentCovariance
+
+    torch.manual_seed(97)
+    head = GaussianHeadWithStateIndependentCovariance(
+        action_size=A, var_type="diagonal", var_func=lambda x: torch.exp(2 * x), var_param_init=-0.25)
+    policy = torch.nn.Sequential(torch.nn.Linear(OBS, 16), torch.nn.Tanh(), torch.nn.Linear(16, A), head)
+    vf = torch.nn.Sequential(torch.nn.Linear(OBS, 16), torch.nn.Tanh(), torch.nn.Linear(16, 1))
+    model = pfrl.nn.Branched(policy, vf)
+    return agents.A2C(model, torch.optim.SGD(model.parameters(), lr=1e-2), gamma=0.99, num_processes=N,
+                      gpu=gpu_id, update_steps=T, use_gae=use_gae, tau=0.95, max_grad_norm=0.5,
+                      entropy_coeff=0.01, fused_loss=fused)
+
+
+def _load_storage(ag, g, pre):
+    """As ``_check_a2c`` does: on the device the "slots" index the recorded states."""
+    dev = ag.device
+    states = torch.as_tensor(g[pre + "states"]).to(dev)
+    actions = torch.as_tensor(g[pre + "actions"]).to(dev)
+    if ag._on_gpu:
+        table = states.reshape((T + 1) * N, OBS)
+        ag._flush_storage(N, 1, actions[0])
+        ag.refs = torch.arange((T + 1) * N, dtype=torch.int32, device=dev).view(T + 1, N, 1)
+        ag._gather = lambda refs, _t=table: _t[refs.reshape(-1).long()]
+    else:
+        ag._flush_storage(N, (OBS,), actions[0])
+        ag.refs = states.clone()
+    ag.actions = actions.reshape(ag.actions.shape).float().clone()
+    ag.rewards = torch.as_tensor(g[pre + "rewards"]).to(dev).clone()
+    ag.masks = torch.as_tensor(g[pre + "masks"]).to(dev).clone()
+    ag.value_preds = torch.as_tensor(g[pre + "value_preds"]).to(dev).clone()
+
+
+def _check_gaussian(gpu_id, fused, seen=None):
+    g = np.load(os.path.join(GOLDEN, "teacher_forced_a2c_gaussian.npz"))
+    n = 0
+    for use_gae in (True, False):
+        tag = "gae%d" % int(use_gae)
+        assert list(g[tag + "_updates"]) == [1, 2, 3]
+        for k in g[tag + "_updates"]:
+            pre = "%s_u%d_" % (tag, k)
+            ag = _gaussian_agent(use_gae, gpu_id, fused)
+            if seen is not None:
+                _watch(ag, seen)
+            assert (ag._head_split() is not None) == (fused and gpu_id >= 0)
+            _load_flat(ag.model, g[pre + "params"])
+            _load_storage(ag, g, pre)
+            ag.update()
+            got = np.asarray([float(v.cpu()) for v in ag._last_losses])
+            np.testing.assert_allclose(got, g[pre + "losses"], rtol=TOL, atol=TOL, err_msg=pre)
+            np.testing.assert_allclose(ag.returns.cpu().numpy(), g[pre + "returns"], rtol=TOL, atol=TOL)
+            np.testing.assert_allclose(_flat(ag), g[pre + "params_after"], rtol=TOL, atol=1e-6, err_msg=pre)
+            stats = [v for _, v in ag.get_statistics()]
+            want = np.float32(1 - np.float32(0.999)) * g[pre + "losses"][[1, 0, 2]]
+            np.testing.assert_allclose(stats, want, rtol=1e-4, atol=2e-3 * TOL, err_msg=pre)
+            n += 1
+    return n
+
+
+def test_gaussian_fixture_on_the_host_route(recorder):
+    assert os.path.getsize(os.path.join(GOLDEN, "teacher_forced_a2c_gaussian.npz")) < 64 * 1024
+    assert _check_gaussian(-1, True) == 6
+    assert not [c for c in recorder.calls if c in LOSS_ENTRY_POINTS]
+
+
+@gpu
+def test_teacher_forced_gaussian_update_on_both_routes(recorder):
+    seen_f, seen_c = [], []
+    assert _check_gaussian(0, True, seen_f) == 6
+    assert recorder.count("pfrl_a2c_gaussian_loss") == 6
+    assert _check_gaussian(0, False, seen_c) == 6
+    assert recorder.count("pfrl_a2c_gaussian_loss") == 6 and recorder.count("pfrl_a2c_loss") == 0
+    # (parameter 4 of the model is the head's var_param: the scale vector's gradient)
+    names = [n for n, _ in _gaussian_agent(True, 0, True).model.named_parameters()]
+    assert any("var_param" in n for n in names) and len(seen_f[0][0]) == len(names)
+    assert all(float(got[names.index(n)].abs().max()) > 0 for got, _ in seen_f for n in names if "var_param" in n)
+    _assert_gradient_condition("gaussian", _errors(seen_f), _errors(seen_c))
+
+
+@gpu
+def test_save_load_round_trip_and_the_next_update(tmp_path):
+    g = np.load(os.path.join(GOLDEN, "teacher_forced_a2c_gaussian.npz"))
+    ag = _gaussian_agent(True, 0, True)
+    _load_flat(ag.model, g["gae1_u1_params"])
+    _load_storage(ag, g, "gae1_u1_")
+    ag.update()
+    ag.save(str(tmp_path / "agent"))
+    assert sorted(os.listdir(str(tmp_path / "agent"))) == ["model.pt", "optimizer.pt"]
+    other = _gaussian_agent(True, 0, True)
+    other.load(str(tmp_path / "agent"))
+    assert np.array_equal(_flat(other), _flat(ag))
+    for a in (ag, other):
+        _load_storage(a, g, "gae1_u2_")
+        a.update()
+    assert np.array_equal(_flat(other), _flat(ag))
+    assert all(torch.equal(x, y) for x, y in zip(ag._last_losses, other._last_losses))
