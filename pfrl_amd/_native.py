@@ -49,10 +49,8 @@ def build(force=False, verbose=False):
     """Compile every HIP source for gfx950 and link libpfrl_amd.so (in-tree)."""
     os.makedirs(LIB_DIR, exist_ok=True)
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "powf_glibc.h"), os.path.join(CSRC, "rms_update.h"),
-                   os.path.join(CSRC, "nhwc.h"), os.path.join(CSRC, "ppo_rows.h"),
-                   os.path.join(CSRC, "gaussian_rows.h"),
-                   os.path.join(_HERE, "..", "include", "pfrl_amd.h"),
+    deps = srcs + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")]
+    deps = deps + [os.path.join(_HERE, "..", "include", "pfrl_amd.h"),
                    os.path.abspath(__file__)]      # (the compiler flags live in this file)
     if not force and os.path.exists(LIB_PATH):
         if all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):

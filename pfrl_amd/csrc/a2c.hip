@@ -12,25 +12,13 @@
 
 #include "common.h"
 #include "gaussian_rows.h"
+#include "row_reduce.h"
+#include "softmax_rows.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxSoftmaxA = 31;
 constexpr int kSums = 3;        // sum adv^2, sum adv lp_a, sum H
-
-// writes the workgroup's n sums: partial[block][n]
-template <int ROWS>
-__device__ __forceinline__ void block_fold(double (&s_red)[ROWS][kThreads / 64], int n,
-                                           double *__restrict__ partial) {
-    __syncthreads();
-    if ((int)threadIdx.x < n) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) t += s_red[threadIdx.x][w];
-        partial[(size_t)blockIdx.x * n + threadIdx.x] = t;
-    }
-}
 
 // The per-row scale factors, each one rounding: inv_m = fl(1 / M), c_pi = fl(pi_coef inv_m),
 // c_v = fl(fl(2 v_coef) inv_m) (the doubling is exact), c_e = fl(ent_coef inv_m).
@@ -47,7 +35,7 @@ __device__ __forceinline__ Coefs coefs_of(int M, float pi_coef, float v_coef, fl
     return c;
 }
 
-// Categorical(logits): lp = log_softmax(z), H = -sum p lp (the row arithmetic of k_reinforce_loss),
+// Categorical(logits): lp = log_softmax(z), H = -sum p lp (softmax_row), and by softmax_grad_row
 //   dlogits_j = c_pi (-adv) (1[j = a] - p_j) + c_e p_j (lp_j + H),   dvalue = c_v (-adv)
 // The action is the float32 A2C.actions stores; it enters through j == a only.
 template <int A>
@@ -66,34 +54,13 @@ __global__ __launch_bounds__(kThreads) void k_a2c_loss(
         for (int j = 0; j < A; ++j) z[j] = logits[(size_t)m * A + j];
         const float af = action[m];
         const int a = (af >= 0.f && af < (float)A) ? (int)af : -1;
-        float mx = z[0];
-#pragma unroll
-        for (int j = 1; j < A; ++j) mx = fmaxf(mx, z[j]);
-        float e[A], sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-            e[j] = expf(z[j] - mx);
-            sum += e[j];
-        }
-        const float lse = mx + logf(sum);
-        float H = 0.f, lpa = 0.f, p[A], lp[A];
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-            lp[j] = z[j] - lse;
-            p[j] = e[j] / sum;
-            H -= p[j] > 0.f ? p[j] * lp[j] : 0.f;
-            if (j == a) lpa = lp[j];
-        }
+        float H, lpa, p[A], lp[A], g[A];
+        softmax_row<A>(z, a, lp, p, H, lpa);
         const float adv = ret[m] - value[m];
         const float neg_adv = -adv;
-        const float gl = c.c_pi * neg_adv;
+        softmax_grad_row<A>(c.c_pi * neg_adv, c.c_e, a, p, lp, H, g);
 #pragma unroll
-        for (int j = 0; j < A; ++j) {
-            const float onehot = j == a ? 1.f : 0.f;
-            float gj = gl * (onehot - p[j]);
-            gj += p[j] > 0.f ? c.c_e * p[j] * (lp[j] + H) : 0.f;
-            dlogits[(size_t)m * A + j] = gj;
-        }
+        for (int j = 0; j < A; ++j) dlogits[(size_t)m * A + j] = g[j];
         dvalue[m] = c.c_v * neg_adv;
         sq = (double)(adv * adv);
         pol = (double)(adv * lpa);
@@ -130,8 +97,7 @@ __global__ __launch_bounds__(kThreads) void k_a2c_gaussian_loss(
     if (live) {
         const Coefs c = coefs_of(M, pi_coef, v_coef, ent_coef);
         const float lpa = row_log_prob(action + base, mean + base, scale, A);
-        double H = 0.0;
-        for (int j = 0; j < A; ++j) H += (double)(kEntropyConst + logf(scale[j]));
+        const double H = gaussian_entropy(scale, A);
         const float adv = ret[m] - value[m];
         const float neg_adv = -adv;
         g = c.c_pi * neg_adv;
@@ -148,18 +114,7 @@ __global__ __launch_bounds__(kThreads) void k_a2c_gaussian_loss(
         s_red[1][wave] = pol;
         s_red[2][wave] = ent;
     }
-    // (A is uniform: every lane of every wave takes part in the shuffles, dead rows add zero)
-    for (int j = 0; j < A; ++j) {
-        double t = 0.0;
-        if (live) {
-            const float s = scale[j];
-            const float d = action[base + j] - mean[base + j];
-            dmean[base + j] = g * (d / (s * s));
-            t = (double)g * ((double)(d * d) / ((double)s * (double)s * (double)s) - 1.0 / (double)s);
-        }
-        t = wave_sum_f64(t);
-        if (lane == 0) s_red[kSums + j][wave] = t;
-    }
+    gaussian_grad_columns(live, g, action, mean, scale, base, A, dmean, s_red, kSums);
     block_fold(s_red, kSums + A, partial);
 }
 
@@ -176,9 +131,7 @@ __global__ __launch_bounds__(64) void k_a2c_finish(const double *__restrict__ pa
     const int lane = threadIdx.x;
     float x[kSums] = {0.f, 0.f, 0.f};
     for (int k = 0; k < kSums + A; ++k) {
-        double s = 0.0;
-        for (int b = lane; b < nblk; b += 64) s += partial[(size_t)b * (kSums + A) + k];
-        s = wave_sum_f64(s);
+        double s = fold_column(partial, nblk, kSums + A, k);
         if (lane != 0) continue;
         if (k == 1) s = -s;
         if (k < kSums) {
@@ -212,13 +165,7 @@ extern "C" int pfrl_a2c_loss(const float *logits, const float *value, const floa
                            logits, value, action, ret, M, pi_coef, v_coef, ent_coef, dlogits,      \
                            dvalue, partial_ws);                                                    \
         break;
-    switch (A) {
-        LOSS_CALL(1) LOSS_CALL(2) LOSS_CALL(3) LOSS_CALL(4) LOSS_CALL(5) LOSS_CALL(6) LOSS_CALL(7)
-        LOSS_CALL(8) LOSS_CALL(9) LOSS_CALL(10) LOSS_CALL(11) LOSS_CALL(12) LOSS_CALL(13) LOSS_CALL(14)
-        LOSS_CALL(15) LOSS_CALL(16) LOSS_CALL(17) LOSS_CALL(18) LOSS_CALL(19) LOSS_CALL(20)
-        LOSS_CALL(21) LOSS_CALL(22) LOSS_CALL(23) LOSS_CALL(24) LOSS_CALL(25) LOSS_CALL(26)
-        LOSS_CALL(27) LOSS_CALL(28) LOSS_CALL(29) LOSS_CALL(30) LOSS_CALL(31)
-    }
+    PFRL_SWITCH_SOFTMAX_A(A, LOSS_CALL)
 #undef LOSS_CALL
     hipLaunchKernelGGL(k_a2c_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, partial_ws, (int)blocks,
                        M, 0, ent_coef, (const float *)nullptr, out3, (float *)nullptr, avg, decay_actor,

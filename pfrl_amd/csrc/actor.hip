@@ -14,17 +14,12 @@
 // All HBM / latency bound elementwise work; every arithmetic step is one rounded f32
 // operation in the order of the PyTorch code it replaces (built with -ffp-contract=off).
 #include "common.h"
+#include "row_reduce.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kChunk = 1024;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---------------------------------------------------------------------------------
 // tanh-squashed diagonal Gaussian: sample and log-probability, one wave per row
@@ -54,8 +49,8 @@ __global__ __launch_bounds__(kThreads) void k_squashed_gaussian_fwd(
         s_ladj += 2.f * (0.6931471805599453f - x - sp);
         s_nlp += nlp;
     }
-    s_ladj = wave_sum(s_ladj);
-    s_nlp = wave_sum(s_nlp);
+    s_ladj = wave_sum_f32(s_ladj);
+    s_nlp = wave_sum_f32(s_nlp);
     if (lane == 0) {
         const float lp = (0.f - s_ladj) + s_nlp;
         logp[row] = lp;
@@ -121,8 +116,8 @@ __global__ __launch_bounds__(kThreads) void k_squashed_head_fwd(
         s_ladj += 2.f * (0.6931471805599453f - u - sp);
         s_nlp += nlp;
     }
-    s_ladj = wave_sum(s_ladj);
-    s_nlp = wave_sum(s_nlp);
+    s_ladj = wave_sum_f32(s_ladj);
+    s_nlp = wave_sum_f32(s_nlp);
     if (lane == 0) {
         const float lp = (0.f - s_ladj) + s_nlp;
         logp[row] = lp;
@@ -319,7 +314,7 @@ __global__ __launch_bounds__(kThreads) void k_adam(AdamArgs a, double lr, double
 // minibatch (256), the cost is the launch, not the arithmetic
 // ---------------------------------------------------------------------------------
 __device__ __forceinline__ float block_sum(float v, float *sh) {
-    v = wave_sum(v);
+    v = wave_sum_f32(v);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
     return (sh[0] + sh[1]) + (sh[2] + sh[3]);

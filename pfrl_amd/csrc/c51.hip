@@ -10,18 +10,13 @@
 // atoms j in increasing j (the reference scatter-adds with atomics in arbitrary
 // order; sums agree to fp32 rounding).
 #include "common.h"
+#include "row_reduce.h"
 
 namespace {
 
 constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxBatch = 4096;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(kThreads) void k_c51_loss(
     const float *__restrict__ q_dist, const int64_t *__restrict__ action,
@@ -74,7 +69,7 @@ __global__ __launch_bounds__(kThreads) void k_c51_loss(
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 if (a0 + u < A) {
-                    const float qv = wave_sum(sv[u] * z);
+                    const float qv = wave_sum_f32(sv[u] * z);
                     if ((a0 + u) == 0 || qv > best) {
                         best = qv;
                         p = pv[u];
@@ -106,8 +101,8 @@ __global__ __launch_bounds__(kThreads) void k_c51_loss(
         // cross entropy against the online distribution of the taken action
         const float yc = fminf(fmaxf(y, 1e-10f), 1.0f);
         const float el = on ? -t * logf(yc) : 0.0f;
-        const float d = wave_sum(el);
-        const float qsa = wave_sum(on ? y * z : 0.0f);
+        const float d = wave_sum_f32(el);
+        const float qsa = wave_sum_f32(on ? y * z : 0.0f);
         float coef = weights != nullptr ? weights[b] : 1.0f;
         if (mean) coef *= inv_b;
         // d/dy of -t*log(clamp(y)): clamp passes the gradient on [1e-10, 1]
@@ -126,7 +121,7 @@ __global__ __launch_bounds__(kThreads) void k_c51_loss(
     if (wave == 0) {
         float acc = 0.0f;
         for (int b = lane; b < B; b += 64) acc += s_part[b];
-        acc = wave_sum(acc);
+        acc = wave_sum_f32(acc);
         if (lane == 0) out_loss[0] = acc;
     }
 }

@@ -40,6 +40,17 @@ void pfrl_profile_events(int kind, int64_t units, hipEvent_t *start, hipEvent_t 
         return 0;                                             \
     } while (0)
 
+// The categorical policy kernels keep a row of A logits in registers, so A is a template parameter:
+// `switch (A)` over 1 .. kMaxSoftmaxA, CASE_(n) being the caller's `case n: launch<n>; break;`.
+constexpr int kMaxSoftmaxA = 31;
+#define PFRL_SWITCH_SOFTMAX_A(A_, CASE_)                                                            \
+    switch (A_) {                                                                                   \
+        CASE_(1) CASE_(2) CASE_(3) CASE_(4) CASE_(5) CASE_(6) CASE_(7) CASE_(8) CASE_(9) CASE_(10)  \
+        CASE_(11) CASE_(12) CASE_(13) CASE_(14) CASE_(15) CASE_(16) CASE_(17) CASE_(18) CASE_(19)   \
+        CASE_(20) CASE_(21) CASE_(22) CASE_(23) CASE_(24) CASE_(25) CASE_(26) CASE_(27) CASE_(28)   \
+        CASE_(29) CASE_(30) CASE_(31)                                                               \
+    }
+
 // ---------------------------------------------------------------------------
 // NEP-50 typed scalars (see include/pfrl_amd.h).  Every arithmetic step is a
 // single correctly-rounded IEEE operation; the file is built with

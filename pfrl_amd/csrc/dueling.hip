@@ -8,17 +8,12 @@
 // One 64-lane wave per sample, lane = atom (n_atoms <= 64), four samples per
 // workgroup; no cross-workgroup traffic.
 #include "common.h"
+#include "row_reduce.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWavesPerBlock = kThreads / 64;
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __device__ __forceinline__ float wmax(float v) {
 #pragma unroll
@@ -57,7 +52,7 @@ __global__ __launch_bounds__(kThreads) void k_dueling_softmax_fwd(
                 const float x = (t[u] - mean) + v;
                 const float m = wmax(on ? x : -INFINITY);
                 const float e = on ? expf(x - m) : 0.0f;
-                const float s = wsum(e);
+                const float s = wave_sum_f32(e);
                 if (on) out[(a0 + u) * Z + lane] = e / s;
             }
         }
@@ -89,7 +84,7 @@ __global__ __launch_bounds__(kThreads) void k_dueling_softmax_bwd(
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             if (a0 + u < A) {
-                const float dot = wsum(on ? g[u] * p[u] : 0.0f);
+                const float dot = wave_sum_f32(on ? g[u] * p[u] : 0.0f);
                 const float gl = on ? p[u] * (g[u] - dot) : 0.0f;
                 colsum += gl;
                 if (on) out[(a0 + u) * Z + lane] = gl;

@@ -23,6 +23,7 @@
 // No float atomics; every sum has a fixed order (k, then j, then the butterfly over i, then
 // b), so the same inputs give the same bits on every run.
 #include "common.h"
+#include "row_reduce.h"
 
 namespace {
 
@@ -30,12 +31,6 @@ constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxBatch = 4096;
 constexpr int kMaxQ = 64;       // N, N', K and A: one lane each
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(kThreads) void k_iqn_loss(
     const float *__restrict__ quantiles, const int64_t *__restrict__ action,
@@ -110,8 +105,8 @@ __global__ __launch_bounds__(kThreads) void k_iqn_loss(
         const bool on = lane < N;
         float coef = weights != nullptr ? weights[b] : 1.0f;
         if (mean) coef = __fmul_rn(coef, inv_b);
-        const float d = wave_sum(on ? el_sum : 0.0f);
-        const float row = wave_sum(on ? __fdiv_rn(el_sum, f_np) : 0.0f);
+        const float d = wave_sum_f32(on ? el_sum : 0.0f);
+        const float row = wave_sum_f32(on ? __fdiv_rn(el_sum, f_np) : 0.0f);
         const float gy = __fmul_rn(__fdiv_rn(g_sum, f_np), coef);
         // the whole [N][A] slice of the gradient: the taken action's column, +0.0 elsewhere
         float *grow = out_grad + (int64_t)b * N * A;
@@ -131,7 +126,7 @@ __global__ __launch_bounds__(kThreads) void k_iqn_loss(
     if (wave == 0) {
         float acc = 0.0f;
         for (int b = lane; b < B; b += 64) acc += s_part[b];
-        acc = wave_sum(acc);
+        acc = wave_sum_f32(acc);
         if (lane == 0) out_loss[0] = acc;
     }
 }

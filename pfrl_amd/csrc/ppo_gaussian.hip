@@ -28,13 +28,9 @@ __global__ __launch_bounds__(kThreads) void k_ppo_gaussian_act(
     if (row >= N) return;
     const size_t base = (size_t)row * A;
     if (z != nullptr) {
-        double H = 0.0;
-        for (int j = 0; j < A; ++j) {
-            const float s = scale[j];
-            action[base + j] = __fadd_rn(__fmul_rn(z[base + j], s), mean[base + j]);
-            H += (double)(kEntropyConst + logf(s));
-        }
-        if (entropy != nullptr) entropy[row] = (float)H;
+        for (int j = 0; j < A; ++j)
+            action[base + j] = __fadd_rn(__fmul_rn(z[base + j], scale[j]), mean[base + j]);
+        if (entropy != nullptr) entropy[row] = (float)gaussian_entropy(scale, A);
     }
     if (given != nullptr) {
         log_prob[row] = row_log_prob(given + base, mean + base, scale, A);
@@ -64,8 +60,7 @@ __global__ __launch_bounds__(kThreads) void k_ppo_gaussian_loss(
     float g_lpa = 0.f;
     if (live) {
         const float lpa = row_log_prob(action + base, mean + base, scale, A);
-        double H = 0.0;
-        for (int j = 0; j < A; ++j) H += (double)(kEntropyConst + logf(scale[j]));
+        const double H = gaussian_entropy(scale, A);
         float surr;
         ppo_surrogate_row(lpa, logp_old[m], adv[m], inv_m, clip_eps, surr, g_lpa);
         float lv, gv;
@@ -83,38 +78,19 @@ __global__ __launch_bounds__(kThreads) void k_ppo_gaussian_loss(
         s_red[1][wave] = val;
         s_red[2][wave] = ent;
     }
-    // (A is uniform: every lane of every wave takes part in the shuffles, dead rows add zero)
-    for (int j = 0; j < A; ++j) {
-        double t = 0.0;
-        if (live) {
-            const float s = scale[j];
-            const float d = action[base + j] - mean[base + j];
-            dmean[base + j] = g_lpa * (d / (s * s));
-            t = (double)g_lpa * ((double)(d * d) / ((double)s * (double)s * (double)s) - 1.0 / (double)s);
-        }
-        t = wave_sum_f64(t);
-        if (lane == 0) s_red[3 + j][wave] = t;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < 3 + A) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) t += s_red[threadIdx.x][w];
-        partial[(size_t)blockIdx.x * (3 + A) + threadIdx.x] = t;
-    }
+    gaussian_grad_columns(live, g_lpa, action, mean, scale, base, A, dmean, s_red, 3);
+    block_fold(s_red, 3 + A, partial);
 }
 
-// out[0] = loss, out[1] = loss_policy, out[2] = loss_value, out[3] = mean entropy (the arithmetic of
-// k_ppo_loss_finish in rollout.hip); dscale[j] = sum over rows - entropy_coef / scale_j
+// out[0] = loss, out[1] = loss_policy, out[2] = loss_value, out[3] = mean entropy
+// (ppo_total_loss, as the categorical finish); dscale[j] = sum over rows - entropy_coef / scale_j
 __global__ __launch_bounds__(64) void k_ppo_gaussian_finish(
     const double *__restrict__ partial, int nblk, int M, int A, float vf_coef, float ent_coef,
     const float *__restrict__ scale, float *__restrict__ out, float *__restrict__ dscale) {
     const int lane = threadIdx.x;
     float head[3] = {0.f, 0.f, 0.f};
     for (int k = 0; k < 3 + A; ++k) {
-        double s = 0.0;
-        for (int b = lane; b < nblk; b += 64) s += partial[(size_t)b * (3 + A) + k];
-        s = wave_sum_f64(s);
+        const double s = fold_column(partial, nblk, 3 + A, k);
         if (k < 3) head[k] = (float)(s / M);
         else if (lane == 0 && dscale != nullptr)
             dscale[k - 3] = (float)(s - (double)ent_coef / (double)scale[k - 3]);
@@ -123,7 +99,7 @@ __global__ __launch_bounds__(64) void k_ppo_gaussian_finish(
         out[1] = head[0];
         out[2] = head[1];
         out[3] = head[2];
-        out[0] = (head[0] + vf_coef * head[1]) + ent_coef * (-head[2]);
+        out[0] = ppo_total_loss(head[0], head[1], head[2], vf_coef, ent_coef);
     }
 }
 

@@ -24,6 +24,13 @@ __device__ __forceinline__ void ppo_surrogate_row(float lpa, float lpo, float ad
     g_lpa = -inv_m * ds * ratio;
 }
 
+// loss = loss_policy + value_func_coef loss_value + entropy_coef loss_entropy on the three float32
+// means, loss_entropy = -mean H, added left to right as ppo.py:665-669 adds them
+__device__ __forceinline__ float ppo_total_loss(float pol, float val, float ent, float vf_coef,
+                                                float ent_coef) {
+    return (pol + vf_coef * val) + ent_coef * (-ent);
+}
+
 // lv = (v - vt)^2, or max((v - vt)^2, (clip(v, vo -+ eps_vf) - vt)^2) when clip_eps_vf >= 0;
 // gv = d lv / d v
 __device__ __forceinline__ void ppo_value_row(float v, float vo, float vt, float clip_eps_vf,

@@ -11,26 +11,14 @@
 
 #include "common.h"
 #include "gaussian_rows.h"
+#include "row_reduce.h"
+#include "softmax_rows.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxSoftmaxA = 31;
 
-// writes the workgroup's 2 + extra sums: partial[block][2 + extra]
-template <int ROWS>
-__device__ __forceinline__ void block_fold(double (&s_red)[ROWS][kThreads / 64], int n,
-                                           double *__restrict__ partial) {
-    __syncthreads();
-    if ((int)threadIdx.x < n) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) t += s_red[threadIdx.x][w];
-        partial[(size_t)blockIdx.x * n + threadIdx.x] = t;
-    }
-}
-
-// Categorical(logits): lp = log_softmax(z), H = -sum p lp (the row arithmetic of k_ppo_loss),
+// Categorical(logits): lp = log_softmax(z), H = -sum p lp (softmax_row), and by softmax_grad_row
 //   dlogits_j = inv_b (-R (1[j = a] - p_j) + beta p_j (lp_j + H))
 template <int A>
 __global__ __launch_bounds__(kThreads) void k_reinforce_loss(
@@ -45,34 +33,13 @@ __global__ __launch_bounds__(kThreads) void k_reinforce_loss(
 #pragma unroll
         for (int j = 0; j < A; ++j) z[j] = logits[(size_t)m * A + j];
         const int a = (int)action[m];
-        float mx = z[0];
-#pragma unroll
-        for (int j = 1; j < A; ++j) mx = fmaxf(mx, z[j]);
-        float e[A], sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-            e[j] = expf(z[j] - mx);
-            sum += e[j];
-        }
-        const float lse = mx + logf(sum);
-        float H = 0.f, lpa = 0.f, p[A], lp[A];
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-            lp[j] = z[j] - lse;
-            p[j] = e[j] / sum;
-            H -= p[j] > 0.f ? p[j] * lp[j] : 0.f;
-            if (j == a) lpa = lp[j];
-        }
+        float H, lpa, p[A], lp[A], g[A];
+        softmax_row<A>(z, a, lp, p, H, lpa);
         const float neg_r = -ret[m];
         // (a NaN return reaches every entry of the row: NaN * 0 is NaN)
-        const float gl = inv_b * neg_r, ge = beta * inv_b;
+        softmax_grad_row<A>(inv_b * neg_r, beta * inv_b, a, p, lp, H, g);
 #pragma unroll
-        for (int j = 0; j < A; ++j) {
-            const float onehot = j == a ? 1.f : 0.f;
-            float gj = gl * (onehot - p[j]);
-            gj += p[j] > 0.f ? ge * p[j] * (lp[j] + H) : 0.f;
-            dlogits[(size_t)m * A + j] = gj;
-        }
+        for (int j = 0; j < A; ++j) dlogits[(size_t)m * A + j] = g[j];
         loss = (double)(neg_r * lpa - beta * H);
         ent = (double)H;
     }
@@ -103,9 +70,7 @@ __global__ __launch_bounds__(kThreads) void k_reinforce_gaussian_loss(
     float g = 0.f;
     if (live) {
         const float lpa = row_log_prob(action + base, mean + base, scale, A);
-        double H = 0.0;
-        for (int j = 0; j < A; ++j) H += (double)(kEntropyConst + logf(scale[j]));
-        const float Hf = (float)H;
+        const float Hf = (float)gaussian_entropy(scale, A);
         const float neg_r = -ret[m];
         g = inv_b * neg_r;
         loss = (double)(neg_r * lpa - beta * Hf);
@@ -117,18 +82,7 @@ __global__ __launch_bounds__(kThreads) void k_reinforce_gaussian_loss(
         s_red[0][wave] = loss;
         s_red[1][wave] = ent;
     }
-    // (A is uniform: every lane of every wave takes part in the shuffles, dead rows add zero)
-    for (int j = 0; j < A; ++j) {
-        double t = 0.0;
-        if (live) {
-            const float s = scale[j];
-            const float d = action[base + j] - mean[base + j];
-            dmean[base + j] = g * (d / (s * s));
-            t = (double)g * ((double)(d * d) / ((double)s * (double)s * (double)s) - 1.0 / (double)s);
-        }
-        t = wave_sum_f64(t);
-        if (lane == 0) s_red[2 + j][wave] = t;
-    }
+    gaussian_grad_columns(live, g, action, mean, scale, base, A, dmean, s_red, 2);
     block_fold(s_red, 2 + A, partial);
 }
 
@@ -141,9 +95,7 @@ __global__ __launch_bounds__(64) void k_reinforce_finish(const double *__restric
                                                          float *__restrict__ dscale) {
     const int lane = threadIdx.x;
     for (int k = 0; k < 2 + A; ++k) {
-        double s = 0.0;
-        for (int b = lane; b < nblk; b += 64) s += partial[(size_t)b * (2 + A) + k];
-        s = wave_sum_f64(s);
+        const double s = fold_column(partial, nblk, 2 + A, k);
         if (lane != 0) continue;
         if (k == 0) out[0] = (float)(s * (double)inv_b);
         else if (k == 1) out[1] = (float)(s / M);
@@ -167,13 +119,7 @@ extern "C" int pfrl_reinforce_loss(const float *logits, const int64_t *action, c
                            (hipStream_t)stream, logits, action, ret, M, inv_batchsize, beta, dlogits, \
                            partial_ws);                                                              \
         break;
-    switch (A) {
-        LOSS_CALL(1) LOSS_CALL(2) LOSS_CALL(3) LOSS_CALL(4) LOSS_CALL(5) LOSS_CALL(6) LOSS_CALL(7)
-        LOSS_CALL(8) LOSS_CALL(9) LOSS_CALL(10) LOSS_CALL(11) LOSS_CALL(12) LOSS_CALL(13) LOSS_CALL(14)
-        LOSS_CALL(15) LOSS_CALL(16) LOSS_CALL(17) LOSS_CALL(18) LOSS_CALL(19) LOSS_CALL(20)
-        LOSS_CALL(21) LOSS_CALL(22) LOSS_CALL(23) LOSS_CALL(24) LOSS_CALL(25) LOSS_CALL(26)
-        LOSS_CALL(27) LOSS_CALL(28) LOSS_CALL(29) LOSS_CALL(30) LOSS_CALL(31)
-    }
+    PFRL_SWITCH_SOFTMAX_A(A, LOSS_CALL)
 #undef LOSS_CALL
     hipLaunchKernelGGL(k_reinforce_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, partial_ws,
                        (int)blocks, M, 0, inv_batchsize, beta, (const float *)nullptr, out2,

@@ -7,6 +7,8 @@
 
 #include "common.h"
 #include "ppo_rows.h"
+#include "row_reduce.h"
+#include "softmax_rows.h"
 
 #include <stdlib.h>
 
@@ -204,11 +206,6 @@ __global__ __launch_bounds__(kThreads) void k_a2c_returns(int64_t T, int64_t N,
     }
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // Stage 1: per-block partial (sum, sum of squares) in f64.
 __global__ __launch_bounds__(kThreads) void k_adv_partial(const float *__restrict__ adv, int64_t n,
                                                           double *__restrict__ partial) {
@@ -220,8 +217,8 @@ __global__ __launch_bounds__(kThreads) void k_adv_partial(const float *__restric
         a += x;
         b += x * x;
     }
-    a = wave_sum(a);
-    b = wave_sum(b);
+    a = wave_sum_f64(a);
+    b = wave_sum_f64(b);
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if ((threadIdx.x & 63) == 0) {
         s1[w] = a;
@@ -247,8 +244,8 @@ __global__ __launch_bounds__(64) void k_adv_final(const double *__restrict__ par
         a += partial[2 * i];
         b += partial[2 * i + 1];
     }
-    a = wave_sum(a);
-    b = wave_sum(b);
+    a = wave_sum_f64(a);
+    b = wave_sum_f64(b);
     if (threadIdx.x == 0) {
         const double mean = a / (double)n;
         double var = b / (double)n - mean * mean;
@@ -293,10 +290,8 @@ __global__ __launch_bounds__(kThreads) void k_ppo_minibatch(
 // against 135 us for the convolution trunk in front of them.
 // One wave per row: lanes split K, A + 1 dot products by wave reduction, then every lane holds the
 // logits; softmax / entropy in registers; the action by inverse CDF on one uniform per row (drawn
-// by the caller: torch's Philox stream, one rand launch).  A <= 31.
+// by the caller: torch's Philox stream, one rand launch).  A <= kMaxSoftmaxA.
 // ---------------------------------------------------------------------------------------
-constexpr int ACT_MAX_OUT = 32;
-
 // (A is a template parameter: with a run-time bound every weight load sits behind a branch and is
 // waited for on the spot -- 20 us for 512 rows; with the loops unrolled at compile time all loads of
 // a 64-column slice are in flight together)
@@ -344,24 +339,10 @@ __global__ __launch_bounds__(256) void k_ppo_act_head(
         }
     }
 #pragma unroll
-    for (int j = 0; j <= A; ++j) {
-        float v = acc[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        acc[j] = v + (j < A ? bp[j] : bv[0]);
-    }
+    for (int j = 0; j <= A; ++j) acc[j] = wave_sum_f32(acc[j]) + (j < A ? bp[j] : bv[0]);
     if (lane != 0) return;
-    float m = acc[0];
-#pragma unroll
-    for (int j = 1; j < A; ++j) m = fmaxf(m, acc[j]);
-    float sum = 0.f;
-    float e[A];
-#pragma unroll
-    for (int j = 0; j < A; ++j) {
-        e[j] = expf(acc[j] - m);
-        sum += e[j];
-    }
-    const float lse = m + logf(sum);
+    float sum, e[A];
+    const float lse = softmax_lse<A>(acc, e, sum);
     // Categorical.entropy(): -sum p log p with log p = logits - logsumexp (probabilities of exactly
     // zero contribute nothing); the action: first j with u * sum < e_0 + .. + e_j
     // (given != NULL: the value pass of an update -- log pi(a | s) of the RECORDED action, no draw)
@@ -410,35 +391,13 @@ __device__ __forceinline__ void ppo_loss_row(const float (&z)[A], float v, int a
                                              float clip_eps_vf, float vf_coef, float ent_coef,
                                              float (&g)[A], float &gv_out, double &pol, double &val,
                                              double &ent) {
-    float mx = z[0];
-#pragma unroll
-    for (int j = 1; j < A; ++j) mx = fmaxf(mx, z[j]);
-    float e[A], sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < A; ++j) {
-        e[j] = expf(z[j] - mx);
-        sum += e[j];
-    }
-    const float lse = mx + logf(sum);
-    float H = 0.f, lpa = 0.f, p[A], lp[A];
-#pragma unroll
-    for (int j = 0; j < A; ++j) {
-        lp[j] = z[j] - lse;
-        p[j] = e[j] / sum;
-        H -= p[j] > 0.f ? p[j] * lp[j] : 0.f;
-        if (j == a) lpa = lp[j];
-    }
+    // (the categorical row: csrc/softmax_rows.h, shared with A2C and REINFORCE)
+    float H, lpa, p[A], lp[A];
+    softmax_row<A>(z, a, lp, p, H, lpa);
     // (clipped surrogate and value loss: csrc/ppo_rows.h, shared with the Gaussian kernels)
     float surr, g_lpa;
     ppo_surrogate_row(lpa, lpo, ad, inv_m, clip_eps, surr, g_lpa);
-    const float ge = ent_coef * inv_m;
-#pragma unroll
-    for (int j = 0; j < A; ++j) {
-        const float onehot = j == a ? 1.f : 0.f;
-        float gj = g_lpa * (onehot - p[j]);
-        gj += p[j] > 0.f ? ge * p[j] * (lp[j] + H) : 0.f;
-        g[j] = gj;
-    }
+    softmax_grad_row<A>(g_lpa, ent_coef * inv_m, a, p, lp, H, g);
     float lv, gv;
     ppo_value_row(v, vo, vt, clip_eps_vf, lv, gv);
     gv_out = vf_coef * inv_m * gv;
@@ -470,25 +429,16 @@ __global__ __launch_bounds__(kThreads) void k_ppo_loss(
         for (int j = 0; j < A; ++j) dlogits[(size_t)m * A + j] = g[j];
         dvalue[m] = gv;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        pol += __shfl_xor(pol, o, 64);
-        val += __shfl_xor(val, o, 64);
-        ent += __shfl_xor(ent, o, 64);
-    }
+    pol = wave_sum_f64(pol);
+    val = wave_sum_f64(val);
+    ent = wave_sum_f64(ent);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) {
         s_red[0][wave] = pol;
         s_red[1][wave] = val;
         s_red[2][wave] = ent;
     }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) t += s_red[threadIdx.x][w];
-        partial[(size_t)blockIdx.x * 3 + threadIdx.x] = t;
-    }
+    block_fold(s_red, 3, partial);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -559,9 +509,7 @@ __global__ __launch_bounds__(256) void k_ppo_head_loss(
                 s = fmaf(hv[q].z, w[j][q].z, s);
                 s = fmaf(hv[q].w, w[j][q].w, s);
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-            z[j] = s + bias[j];
+            z[j] = wave_sum_f32(s) + bias[j];
         }
         float zl[A], g[A], gv;
 #pragma unroll
@@ -631,23 +579,17 @@ __global__ __launch_bounds__(256) void k_ppo_head_loss(
 __global__ __launch_bounds__(64) void k_ppo_loss_finish(const double *__restrict__ partial, int nblk,
                                                         int M, float vf_coef, float ent_coef,
                                                         float *__restrict__ out) {
-    const int lane = threadIdx.x;
-    double s[3] = {0.0, 0.0, 0.0};
-    for (int b = lane; b < nblk; b += 64) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) s[k] += partial[(size_t)b * 3 + k];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
-    }
-    if (lane == 0) {
-        const float pol = (float)(s[0] / M), val = (float)(s[1] / M), ent = (float)(s[2] / M);
+    // (a column's sum is the lane's sequential sum in b order, then the butterfly: the same bits
+    // whether the three columns are folded one after the other or side by side in one loop over b)
+    const double s0 = fold_column(partial, nblk, 3, 0);
+    const double s1 = fold_column(partial, nblk, 3, 1);
+    const double s2 = fold_column(partial, nblk, 3, 2);
+    if (threadIdx.x == 0) {
+        const float pol = (float)(s0 / M), val = (float)(s1 / M), ent = (float)(s2 / M);
         out[1] = pol;
         out[2] = val;
         out[3] = ent;
-        out[0] = (pol + vf_coef * val) + ent_coef * (-ent);
+        out[0] = ppo_total_loss(pol, val, ent, vf_coef, ent_coef);
     }
 }
 
@@ -775,7 +717,7 @@ extern "C" int pfrl_ppo_act_head(const float *h, const float *w_policy, const fl
                                  const int64_t *given_action, int64_t *out_action, float *out_entropy,
                                  float *out_value, float *out_log_prob, int32_t N, int32_t K, int32_t A,
                                  const int32_t *rows, void *stream) {
-    PFRL_CHECK_ARG(N >= 0 && K >= 1 && A >= 1 && A < ACT_MAX_OUT, "pfrl_ppo_act_head: 1 <= A <= 31");
+    PFRL_CHECK_ARG(N >= 0 && K >= 1 && A >= 1 && A <= kMaxSoftmaxA, "pfrl_ppo_act_head: 1 <= A <= 31");
     PFRL_CHECK_ARG(h && w_policy && b_policy && w_value && b_value && out_value,
                    "pfrl_ppo_act_head: null pointer");
     PFRL_CHECK_ARG(given_action != nullptr || (u01 != nullptr && out_action != nullptr),
@@ -788,13 +730,7 @@ extern "C" int pfrl_ppo_act_head(const float *h, const float *w_policy, const fl
                            given_action, out_action, out_entropy, out_value, out_log_prob, N, K,  \
                            rows);                                                                 \
         break;
-    switch (A) {
-        ACT_CALL(1) ACT_CALL(2) ACT_CALL(3) ACT_CALL(4) ACT_CALL(5) ACT_CALL(6) ACT_CALL(7) ACT_CALL(8)
-        ACT_CALL(9) ACT_CALL(10) ACT_CALL(11) ACT_CALL(12) ACT_CALL(13) ACT_CALL(14) ACT_CALL(15)
-        ACT_CALL(16) ACT_CALL(17) ACT_CALL(18) ACT_CALL(19) ACT_CALL(20) ACT_CALL(21) ACT_CALL(22)
-        ACT_CALL(23) ACT_CALL(24) ACT_CALL(25) ACT_CALL(26) ACT_CALL(27) ACT_CALL(28) ACT_CALL(29)
-        ACT_CALL(30) ACT_CALL(31)
-    }
+    PFRL_SWITCH_SOFTMAX_A(A, ACT_CALL)
 #undef ACT_CALL
     PFRL_LAUNCH_CHECK();
 }
@@ -805,7 +741,7 @@ extern "C" int pfrl_ppo_loss(const float *logits, const float *value, const int6
                              float clip_eps_vf, float value_func_coef, float entropy_coef,
                              float *dlogits, float *dvalue, double *partial_ws, float *out4,
                              void *stream) {
-    PFRL_CHECK_ARG(M >= 1 && A >= 1 && A < ACT_MAX_OUT, "pfrl_ppo_loss: 1 <= A <= 31, M >= 1");
+    PFRL_CHECK_ARG(M >= 1 && A >= 1 && A <= kMaxSoftmaxA, "pfrl_ppo_loss: 1 <= A <= 31, M >= 1");
     PFRL_CHECK_ARG(logits && value && action && adv && log_prob_old && v_teacher && dlogits && dvalue &&
                        partial_ws && out4 && (clip_eps_vf < 0.f || v_pred_old),
                    "pfrl_ppo_loss: null pointer");
@@ -817,13 +753,7 @@ extern "C" int pfrl_ppo_loss(const float *logits, const float *value, const int6
                            clip_eps, clip_eps_vf, value_func_coef, entropy_coef, dlogits, dvalue,  \
                            partial_ws);                                                            \
         break;
-    switch (A) {
-        LOSS_CALL(1) LOSS_CALL(2) LOSS_CALL(3) LOSS_CALL(4) LOSS_CALL(5) LOSS_CALL(6) LOSS_CALL(7)
-        LOSS_CALL(8) LOSS_CALL(9) LOSS_CALL(10) LOSS_CALL(11) LOSS_CALL(12) LOSS_CALL(13) LOSS_CALL(14)
-        LOSS_CALL(15) LOSS_CALL(16) LOSS_CALL(17) LOSS_CALL(18) LOSS_CALL(19) LOSS_CALL(20)
-        LOSS_CALL(21) LOSS_CALL(22) LOSS_CALL(23) LOSS_CALL(24) LOSS_CALL(25) LOSS_CALL(26)
-        LOSS_CALL(27) LOSS_CALL(28) LOSS_CALL(29) LOSS_CALL(30) LOSS_CALL(31)
-    }
+    PFRL_SWITCH_SOFTMAX_A(A, LOSS_CALL)
 #undef LOSS_CALL
     hipLaunchKernelGGL(k_ppo_loss_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, partial_ws,
                        (int)blocks, M, value_func_coef, entropy_coef, out4);

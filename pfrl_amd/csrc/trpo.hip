@@ -81,27 +81,8 @@ __global__ __launch_bounds__(kThreads) void k_trpo_gaussian_eval(
         s_red[1][wave] = kl;
     }
     const int cols = dmean != nullptr ? 2 + A : 2;
-    if (dmean != nullptr) {
-        // (A is uniform: every lane of every wave takes part in the shuffles, dead rows add zero)
-        for (int j = 0; j < A; ++j) {
-            double t = 0.0;
-            if (live) {
-                const float s = scale[j];
-                const float d = action[base + j] - mean[base + j];
-                dmean[base + j] = g * (d / (s * s));
-                t = (double)g * ((double)(d * d) / ((double)s * (double)s * (double)s) - 1.0 / (double)s);
-            }
-            t = wave_sum_f64(t);
-            if (lane == 0) s_red[2 + j][wave] = t;
-        }
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < cols) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) t += s_red[threadIdx.x][w];
-        partial[(size_t)blockIdx.x * (2 + A) + threadIdx.x] = t;
-    }
+    if (dmean != nullptr) gaussian_grad_columns(live, g, action, mean, scale, base, A, dmean, s_red, 2);
+    block_fold(s_red, cols, partial, 2 + A);
 }
 
 // out3 = {gain, mean KL, mean entropy}; dscale[j] when asked for
@@ -113,14 +94,14 @@ __global__ __launch_bounds__(64) void k_trpo_gaussian_finish(
     const int cols = dscale != nullptr ? 2 + A : 2;
     double head[2] = {0.0, 0.0};
     for (int k = 0; k < cols; ++k) {
-        double s = 0.0;
-        for (int b = lane; b < nblk; b += 64) s += partial[(size_t)b * (2 + A) + k];
-        s = wave_sum_f64(s);
+        const double s = fold_column(partial, nblk, 2 + A, k);
         if (k < 2) head[k] = s;
         else if (lane == 0)
             dscale[k - 2] = (float)(s + (double)ent_coef / (double)scale[k - 2]);
     }
     if (lane == 0) {
+        // (the terms and the order of gaussian_entropy, inside the one pass over scale that this
+        // single lane makes: a second loop costs it 32 more dependent loads)
         double H = 0.0, kl_scale = 0.0;
         for (int j = 0; j < A; ++j) {
             H += (double)(kEntropyConst + logf(scale[j]));
