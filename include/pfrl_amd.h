@@ -953,6 +953,36 @@ int pfrl_sac_policy_loss_bwd(const float *g_loss, const float *q1, const float *
                              const float *log_temperature, float temperature, float *g_log_prob,
                              float *g_q1, float *g_q2, int32_t B, void *stream);
 
+/* TD3 / DDPG: what lies between the network outputs and backward() (pfrl/agents/td3.py,
+ * pfrl/agents/ddpg.py), float32 vectors, each entry point ONE launch.  Arguments outside the stated
+ * gates return PFRL_ERR_ARG before anything is launched or written.
+ * pfrl_td3_smooth_action (td3.py:22-25, default_target_policy_smoothing_func behind its draw):
+ *   out[i] = clamp(action[i] + clamp(sigma * noise[i], -noise_clip, noise_clip), low, high) for n
+ *   floats, clamp being torch.clamp (a NaN passes through), every step one rounded float32
+ *   operation; out may be noise (in place).  n >= 1, sigma >= 0, noise_clip >= 0, low <= high.
+ * pfrl_td3_critic_loss (td3.py:191-211 with n_q = 2, ddpg.py:158-168 with n_q = 1; next_q, pred,
+ *   loss, unit_g_pred: host arrays of n_q device pointers):
+ *   t = reward + (d * (1 - terminal)) * nq, nq = next_q[0] or the NaN-propagating
+ *   min(next_q[0], next_q[1]), d = discount[i] or, when discount is NULL, the float gamma (DDPG's
+ *   self.gamma); loss[k][0] = mean((t - pred[k])^2) (F.mse_loss: the whole mean, not SAC's half);
+ *   unit_g_pred[k] (entry or array may be NULL): d loss[k] / d pred[k] for an upstream gradient of
+ *   exactly 1; target_q (may be NULL) receives t.  One workgroup per critic, a fixed reduction order.
+ *   1 <= B <= 65536, n_q in {1, 2}.
+ * pfrl_td3_critic_loss_bwd: g_pred[k][i] = -(g_loss[k][0] * ((2 (target_q[i] - pred[k][i])) / B));
+ *   a NULL g_loss[k] gives zeros; g_loss[k][0] == 1 gives unit_g_pred[k] bit for bit.
+ * pfrl_neg_mean (td3.py:238-242, ddpg.py:179-182): loss[0] = -(sum(q) / B), unit_g_q[i] = -(1 / B)
+ *   (may be NULL).  1 <= B <= 65536. */
+int pfrl_td3_smooth_action(const float *action, const float *noise, float sigma, float noise_clip,
+                           float low, float high, float *out, int64_t n, void *stream);
+int pfrl_td3_critic_loss(const float *reward, const float *discount, float gamma, const float *terminal,
+                         const float *const *next_q, const float *const *pred, int32_t n_q,
+                         float *target_q, float *const *loss, float *const *unit_g_pred, int32_t B,
+                         void *stream);
+int pfrl_td3_critic_loss_bwd(const float *const *g_loss, const float *target_q,
+                             const float *const *pred, float *const *g_pred, int32_t n_q, int32_t B,
+                             void *stream);
+int pfrl_neg_mean(const float *q, float *loss, float *unit_g_q, int32_t B, void *stream);
+
 /* Ragged gather of sampled episodes for recurrent updates: batch_recurrent_experiences
  * (pfrl/replay_buffer.py:219-287) over EpisodicReplayBuffer.sample_episodes (pfrl/replay_buffers/
  * episodic.py:48-85, windows cut by random_subseq).  An episode is a run of consecutive

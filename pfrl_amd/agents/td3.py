@@ -6,6 +6,13 @@ with the delayed policy / target update (:239-246), statistics (:319-328).  The
 replay side is the HBM store shared with DQN / SAC (float32 vector observations
 and actions); the whole update replays as a HIP graph, one graph for each of the
 two step shapes (critics only; critics + policy + soft target sync).
+
+With ``fused_loss`` (the default) on a GPU, what lies between the network outputs and
+``backward()`` runs as the launches of ``csrc/td3.hip`` (:mod:`pfrl_amd.agents._td3_losses`):
+target-policy smoothing in place on the noise draw, the critic target with both MSE losses and
+their gradients, the policy loss with its gradient; the two critics and the two target critics each
+run as one chain of launches when ``nn.twin_mlp.twin_plan`` admits the pair.  A subclass that
+overrides ``update_q_func`` / ``update_policy`` keeps the torch expressions of that method.
 """
 import copy
 from logging import getLogger
@@ -13,7 +20,10 @@ from logging import getLogger
 import torch
 from torch.nn import functional as F
 
+from pfrl_amd import _native
+from pfrl_amd.agents import _td3_losses
 from pfrl_amd.agents._replay_actor_critic import ReplayActorCritic
+from pfrl_amd.agents.soft_actor_critic import SoftActorCritic
 from pfrl_amd.utils.batch_states import batch_states
 from pfrl_amd.utils.clip_l2_grad_norm import clip_l2_grad_norm_
 from pfrl_amd.utils.contexts import evaluating
@@ -39,7 +49,7 @@ class TD3(ReplayActorCritic):
                  logger=getLogger(__name__), batch_states=batch_states, burnin_action_func=None,
                  policy_update_delay=2,
                  target_policy_smoothing_func=default_target_policy_smoothing_func,
-                 use_graphs=None):
+                 use_graphs=None, fused_loss=True):
         self.policy, self.q_func1, self.q_func2 = policy, q_func1, q_func2
         self.policy_optimizer = policy_optimizer
         self.q_func1_optimizer = q_func1_optimizer
@@ -48,6 +58,7 @@ class TD3(ReplayActorCritic):
         self.max_grad_norm = max_grad_norm
         self.policy_update_delay = policy_update_delay
         self.target_policy_smoothing_func = target_policy_smoothing_func
+        self.fused_loss = fused_loss
         self.policy_n_updates = 0
         self.q_func_n_updates = 0
         # n_times_update is accepted and ignored, as in the reference (:118-126)
@@ -92,7 +103,62 @@ class TD3(ReplayActorCritic):
             clip_l2_grad_norm_(module.parameters(), self.max_grad_norm)
         optimizer.step()
 
+    def _fused(self, method):
+        """Does ``method`` run on the launches of csrc/td3.hip?  The flag, a GPU, the library, and
+        nobody overrode the method (an override may rely on the statements it replaces)."""
+        return (self.fused_loss and self.device.type == "cuda" and _native.available()
+                and getattr(type(self), method) is getattr(TD3, method))
+
+    def _backward_unit(self, losses):
+        """backward of scalar losses with dL/dL = 1 from the tensor the loss nodes recognise (their
+        forward launch has then written the gradients already)."""
+        if all(l.dim() == 0 and l.dtype == torch.float32 for l in losses):
+            one = _td3_losses.unit_grad(self.device)
+            torch.autograd.backward(list(losses), [one] * len(losses))
+        else:
+            torch.autograd.backward(list(losses))
+
+    def _update_q_func_fused(self, batch):
+        q_pair = SoftActorCritic._q_pair
+        next_state = batch["next_state"]
+        with torch.no_grad(), evaluating(self.target_policy), evaluating(self.target_q_func1), \
+                evaluating(self.target_q_func2):
+            next_actions = self.target_policy(next_state).sample()
+            if self.target_policy_smoothing_func is default_target_policy_smoothing_func:
+                # the same one draw of the same shape (the device generator advances as in the
+                # default function), then its three elementwise steps as one launch in place
+                noise = torch.randn_like(next_actions)
+                next_actions = _td3_losses.smooth_action(next_actions, noise, 0.2, 0.5, -1, 1,
+                                                         out=noise)
+            else:
+                next_actions = self.target_policy_smoothing_func(next_actions)
+            next_q1, next_q2, _ = q_pair(self.target_q_func1, self.target_q_func2,
+                                         (next_state, next_actions))
+        predict_q1, predict_q2, _ = q_pair(self.q_func1, self.q_func2,
+                                           (batch["state"], batch["action"]))
+        predict_q1, predict_q2 = torch.flatten(predict_q1), torch.flatten(predict_q2)
+        loss1, loss2 = _td3_losses.critic_losses(
+            batch["reward"], batch["discount"], batch["is_state_terminal"],
+            (torch.flatten(next_q1), torch.flatten(next_q2)), (predict_q1, predict_q2))
+        self._stat(q1=predict_q1, q2=predict_q2, loss1=loss1, loss2=loss2)
+        # One backward pass for both losses, then the two optimizer steps.  Same gradients and
+        # parameters as the reference's q1-then-q2 order: neither loss depends on the other
+        # network, and both predictions were computed before either step there too (:207-229).
+        self.q_func1_optimizer.zero_grad()
+        self.q_func2_optimizer.zero_grad()
+        self._backward_unit([loss1, loss2])
+        for module in (self.q_func1, self.q_func2):
+            self._reducers[module].all_reduce()
+            if self.max_grad_norm is not None:
+                clip_l2_grad_norm_(module.parameters(), self.max_grad_norm)
+        from pfrl_amd.optimizers import FusedAdam
+
+        # (one launch for both when they are FusedAdam with equal hyperparameters, else q1, q2)
+        FusedAdam.step_together([self.q_func1_optimizer, self.q_func2_optimizer])
+
     def update_q_func(self, batch):
+        if self._fused("update_q_func"):
+            return self._update_q_func_fused(batch)
         next_state = batch["next_state"]
         with torch.no_grad(), evaluating(self.target_policy), evaluating(self.target_q_func1), \
                 evaluating(self.target_q_func2):
@@ -113,6 +179,16 @@ class TD3(ReplayActorCritic):
     def update_policy(self, batch):
         state = batch["state"]
         q = self.q_func1((state, self.policy(state).rsample()))
+        if self._fused("update_policy"):
+            loss = _td3_losses.neg_mean(q)
+            self._stat(policy_loss=loss)
+            self.policy_optimizer.zero_grad()
+            self._backward_unit([loss])
+            self._reducers[self.policy].all_reduce()
+            if self.max_grad_norm is not None:
+                clip_l2_grad_norm_(self.policy.parameters(), self.max_grad_norm)
+            self.policy_optimizer.step()
+            return
         loss = -torch.mean(q)
         self._stat(policy_loss=loss)
         self._step(loss, self.policy, self.policy_optimizer)

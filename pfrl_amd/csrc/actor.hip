@@ -313,17 +313,7 @@ __global__ __launch_bounds__(kThreads) void k_adam(AdamArgs a, double lr, double
 // SAC losses (pfrl/agents/soft_actor_critic.py:214-308), each a single workgroup: B is the
 // minibatch (256), the cost is the launch, not the arithmetic
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ float block_sum(float v, float *sh) {
-    v = wave_sum_f32(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-__device__ __forceinline__ float torch_min(float a, float b) {   // NaN-propagating, as torch.min
-    return (a < b || a != a) ? a : b;
-}
-
+// (block_sum and torch_min: row_reduce.h, shared with td3.hip)
 __device__ __forceinline__ float temperature_of(const float *log_t, float t_val) {
     return log_t != nullptr ? expf(*log_t) : t_val;   // TemperatureHolder: exp(log_temperature)
 }

@@ -21,6 +21,19 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
     return v;
 }
 
+// The sum of a 256-thread workgroup (four waves) in every thread: butterfly per wave, then the four
+// wave sums folded pairwise through sh[4].
+__device__ __forceinline__ float block_sum(float v, float *sh) {
+    v = wave_sum_f32(v);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+__device__ __forceinline__ float torch_min(float a, float b) {   // NaN-propagating, as torch.min
+    return (a < b || a != a) ? a : b;
+}
+
 // s_red[k][w] holds wave w's sum of quantity k (written by lane 0 of each wave).  Thread k < n adds
 // the waves of row k in wave order and writes partial[block][k]; the rows of partial are `cols`
 // wide (n when not given: a kernel that fills only the head of its rows passes the full width).
