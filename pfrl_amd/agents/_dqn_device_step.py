@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from pfrl_amd import _native, host_plan, ops
+from pfrl_amd.agents._policy_split import prefix_view
 from pfrl_amd.device_store import DeviceActions, DeviceObsBatch
 from pfrl_amd.staging import StagingRing
 from pfrl_amd.utils.contexts import evaluating
@@ -94,10 +95,7 @@ def act_split(agent):
         lin = model[len(model) - 2]
         if (isinstance(lin, nn.Linear) and 1 <= lin.out_features <= 16
                 and lin.weight.dtype == torch.float32 and lin.weight.is_contiguous()):
-            body = object.__new__(type(model))
-            body.__dict__ = dict(model.__dict__)
-            body._modules = collections.OrderedDict(list(model._modules.items())[:-2])
-            out = (body, lin)
+            out = (prefix_view(model, drop=2), lin)
     agent._act_split_cache = (model, out, tuple(id(m) for m in model.children()))
     return out
 

@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from pfrl_amd import agent, ops
+from pfrl_amd.agents import _policy_split
 from pfrl_amd.device_store import DeviceObsBatch
 from pfrl_amd.utils.batch_states import batch_states
 from pfrl_amd.utils.clip_l2_grad_norm import clip_l2_grad_norm_
@@ -179,8 +180,8 @@ class A2C(agent.AttributeSavingMixin, agent.BatchAgent):
                 self.returns[i] = self.rewards[i] + self.gamma * self.returns[i + 1] * self.masks[i]
 
     def _head_split(self):
-        """How the fused loss launch runs behind ``self.model``, by the splits PPO and REINFORCE use
-        (``_ActGraph._split`` / ``_gaussian_split``; A2C's model already has the shape they expect):
+        """How the fused loss launch runs behind ``self.model`` (``_policy_split.softmax_actor_critic``
+        / ``gaussian_actor_critic``):
 
           ("softmax", heads, None)       ``Sequential(body..., Branched(Sequential(Linear(K, A <= 31),
                                          SoftmaxCategoricalHead()), Linear(K, 1)))``
@@ -194,13 +195,9 @@ class A2C(agent.AttributeSavingMixin, agent.BatchAgent):
             return None
         if self._split is not None and self._split[0] is self.model:
             return self._split[1]
-        from pfrl_amd.agents.ppo import _ActGraph
-        from pfrl_amd.agents.reinforce import _PolicyOnly
-
         out = None
         if all(p.dtype == torch.float32 for p in self.model.parameters()):
-            graph = _ActGraph(_PolicyOnly(self.model, self.device))
-            found = graph._split()
+            found = _policy_split.softmax_actor_critic(self.model)
             if found is not None:
                 body, pol, val = found
 
@@ -210,10 +207,9 @@ class A2C(agent.AttributeSavingMixin, agent.BatchAgent):
 
                 out = ("softmax", heads, None)
             else:
-                found = graph._gaussian_split()
+                found = _policy_split.gaussian_actor_critic(self.model, self.device)
                 if found is not None:
-                    view, head = found
-                    out = ("gaussian", view, lambda A: graph.gaussian_scale(head, A))
+                    out = ("gaussian", found.view, found.scale)
         self._split = (self.model, out)
         return out
 
@@ -240,7 +236,7 @@ class A2C(agent.AttributeSavingMixin, agent.BatchAgent):
                                                decay=decay)
             torch.autograd.backward([head_out, values], [dhead, dvalue])
         else:
-            scale = scale_of(A)
+            scale = scale_of()
             out3, dhead, dvalue, dscale = ops.a2c_gaussian_loss(
                 head_out, scale, values, actions, ret, *coefs, avg=self._avg, decay=decay,
                 want_dscale=scale.requires_grad)

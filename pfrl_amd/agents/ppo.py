@@ -35,6 +35,7 @@ import torch
 import torch.nn.functional as F
 
 from pfrl_amd import agent, ops
+from pfrl_amd.agents import _policy_split
 from pfrl_amd.agents.dqn import _DeviceRecord, _mean_or_nan
 from pfrl_amd.utils.clip_l2_grad_norm import clip_grad_norm_device_
 from pfrl_amd.device_store import DeviceObs, DeviceObsBatch
@@ -241,50 +242,25 @@ class _ActGraph:
     def _split(self):
         """(body, policy layer, value layer) when the model is ``Sequential(..., Branched(Sequential(
         Linear(K, A), SoftmaxCategoricalHead()), Linear(K, 1)))`` -- the example network
-        (examples/atari/train_ppo_ale.py:247-264): its two narrow heads, the sampling and the
-        entropy then run as ONE launch (pfrl_ppo_act_head).  ``body`` is a view of the model without
-        its last child (same class, same children and parameters, so a fused trunk stays fused)."""
+        (``_policy_split.softmax_actor_critic``): its two narrow heads, the sampling and the entropy
+        then run as ONE launch (pfrl_ppo_act_head).  ``body`` is a view of the model without its last
+        child (same class, same children and parameters, so a fused trunk stays fused).
+        ``PFRL_PPO_ACT_HEAD=0``: None."""
         model = self.agent.model
         hit = self.__dict__.get("_split_cache")
         if hit is not None and hit[0] is model:
             return hit[1]
-        import collections
-
-        from pfrl_amd.nn import Branched
-        from pfrl_amd.policies import SoftmaxCategoricalHead
-
         out = None
-        nn = torch.nn
-        if (os.environ.get("PFRL_PPO_ACT_HEAD", "1") != "0" and isinstance(model, nn.Sequential)
-                and len(model) >= 2 and type(model[len(model) - 1]) is Branched):
-            kids = list(model[len(model) - 1].child_modules)
-            if len(kids) == 2 and type(kids[0]) is nn.Sequential and len(kids[0]) == 2:
-                pol, head, val = kids[0][0], kids[0][1], kids[1]
-                if (isinstance(pol, nn.Linear) and type(head) is SoftmaxCategoricalHead
-                        and isinstance(val, nn.Linear) and val.out_features == 1
-                        and pol.in_features == val.in_features and 1 <= pol.out_features <= 31
-                        and pol.bias is not None and val.bias is not None
-                        and pol.weight.dtype == torch.float32):
-                    body = object.__new__(type(model))
-                    body.__dict__ = dict(model.__dict__)
-                    body._modules = collections.OrderedDict(list(model._modules.items())[:-1])
-                    out = (body, pol, val)
+        if os.environ.get("PFRL_PPO_ACT_HEAD", "1") != "0":
+            out = _policy_split.softmax_actor_critic(model)
         self._split_cache = (model, out)
         return out
 
-    def _gaussian_split(self):
-        """(head-less model, head) when the policy branch ends in a Gaussian head whose scale does not
-        depend on the state -- ``GaussianHeadWithStateIndependentCovariance`` (spherical or diagonal,
-        any ``var_func``) or ``GaussianHeadWithFixedCovariance`` -- behind a ``Linear(., A)``,
-        A <= 32, in one of the two model shapes in use: the reference example's
-        ``Branched(Sequential(..., Linear(., A), head), value branch)``
-        (examples/mujoco/reproduction/ppo/train_ppo.py:153-189) or ``Sequential(body...,
-        Branched(Sequential(..., Linear(., A), head), value branch))``.  The head-less model is a
-        view built like ``_split``'s body (same classes, same children and parameters) that yields
-        ``(mean [M, A], value [M, 1])``; sampling, entropy, log-probability and the loss then run
-        as fused launches (csrc/ppo_gaussian.hip).  None for anything else -- a state-dependent
-        variance, recurrent models, non-f32 parameters, a subclassed or instance-patched
-        ``_lossfun`` / ``_sample_action`` -- which keeps torch.distributions + autograd."""
+    def _gaussian(self):
+        """``_policy_split.gaussian_actor_critic`` of the agent's model: a policy branch that ends in
+        ``Linear(., A <= 32)`` and a Gaussian head whose scale does not depend on the state.  None
+        for anything else, and for what the fused launches do not restate: recurrent models, a
+        subclassed or instance-patched ``_lossfun`` / ``_sample_action``."""
         ag = self.agent
         if (ag.recurrent or type(ag)._lossfun is not PPO._lossfun or "_lossfun" in ag.__dict__
                 or type(ag)._sample_action is not PPO._sample_action
@@ -294,75 +270,22 @@ class _ActGraph:
         hit = self.__dict__.get("_gaussian_cache")
         if hit is not None and hit[0] is model:
             return hit[1]
-        import collections
-
-        from pfrl_amd.nn import Branched
-        from pfrl_amd.policies import (GaussianHeadWithFixedCovariance,
-                                       GaussianHeadWithStateIndependentCovariance)
-
-        nn = torch.nn
-
-        def without_last(seq, replacement=None):
-            view = object.__new__(type(seq))
-            view.__dict__ = dict(seq.__dict__)
-            items = list(seq._modules.items())
-            last = [] if replacement is None else [(items[-1][0], replacement)]
-            view._modules = collections.OrderedDict(items[:-1] + last)
-            return view
-
-        def strip(branched):
-            """(Branched view whose policy branch ends at its Linear, head) or None."""
-            kids = list(branched.child_modules)
-            if len(kids) != 2 or type(kids[0]) is not nn.Sequential or len(kids[0]) < 2:
-                return None
-            pol, head = kids[0][len(kids[0]) - 2], kids[0][len(kids[0]) - 1]
-            if type(head) not in (GaussianHeadWithStateIndependentCovariance,
-                                  GaussianHeadWithFixedCovariance):
-                return None
-            if not (isinstance(pol, nn.Linear) and 1 <= pol.out_features <= ops.GAUSSIAN_MAX_A):
-                return None
-            view = object.__new__(type(branched))
-            view.__dict__ = dict(branched.__dict__)
-            view._modules = collections.OrderedDict(
-                child_modules=nn.ModuleList([without_last(kids[0]), kids[1]]))
-            return view, head, pol.out_features
-
-        out = None
-        found = None
-        if type(model) is Branched:
-            found = strip(model)
-            if found is not None:
-                out = (found[0], found[1])
-        elif (isinstance(model, nn.Sequential) and len(model) >= 2
-                and type(model[len(model) - 1]) is Branched):
-            found = strip(model[len(model) - 1])
-            if found is not None:
-                out = (without_last(model, replacement=found[0]), found[1])
-        if out is not None and not all(p.dtype == torch.float32 for p in model.parameters()):
-            out = None
-        if out is not None:
-            head, A = out[1], found[2]
-            if type(head) is GaussianHeadWithFixedCovariance:
-                # a constant: built once, outside any capture
-                const = torch.as_tensor(head.scale, dtype=torch.float32).to(ag.device)
-                if const.numel() not in (1, A) or bool((const <= 0).any()):
-                    out = None
-                else:
-                    self._fixed_scale = const.reshape(-1).expand(A).contiguous()
-            elif head.var_param.numel() not in (1, A):
-                out = None
+        out = _policy_split.gaussian_actor_critic(model, ag.device)
         self._gaussian_cache = (model, out)
         return out
 
-    def gaussian_scale(self, head, A):
-        """The policy's scale vector [A]: ``sqrt(var_func(var_param))`` computed by torch, so that any
-        ``var_func`` works and its gradient is ``scale.backward(dscale)`` (a spherical variance
-        expands to A equal entries); the constant of a fixed-covariance head."""
-        from pfrl_amd.policies import GaussianHeadWithFixedCovariance
+    def _gaussian_split(self):
+        """(head-less model, head) of ``_gaussian()``: the view yields ``(mean [M, A], value [M, 1])``;
+        sampling, entropy, log-probability and the loss then run as fused launches
+        (csrc/ppo_gaussian.hip).  None keeps torch.distributions + autograd."""
+        found = self._gaussian()
+        return None if found is None else (found.view, found.head)
 
-        if type(head) is GaussianHeadWithFixedCovariance:
-            return self._fixed_scale
-        return torch.sqrt(head.var_func(head.var_param)).reshape(-1).expand(A)
+    def gaussian_scale(self, head, A):
+        """The scale vector [A] of the recognised policy (``GaussianSplit.scale``)."""
+        found = self._gaussian()
+        assert found.head is head and found.A == A
+        return found.scale()
 
     def gaussian_act_split(self):
         """``_gaussian_split()`` where the fused acting / value-pass launch applies

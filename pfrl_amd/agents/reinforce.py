@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from pfrl_amd import agent, ops
-from pfrl_amd.agents.ppo import PPO, _ActGraph
+from pfrl_amd.agents import _policy_split
 from pfrl_amd.agents.trpo import _clip_l2_grad_norm_host_
 from pfrl_amd.utils.batch_states import batch_states
 from pfrl_amd.utils.mode_of_distribution import mode_of_distribution
@@ -46,52 +46,22 @@ def returns_of(r_seq):
     return np.cumsum(list(reversed(r_seq[1:])))[::-1]
 
 
-class _PolicyOnly:
-    """What ``_ActGraph``'s head splits read of a PPO agent, around a model that PPO's model shapes
-    contain as the policy branch."""
-
-    _lossfun = PPO._lossfun
-    _sample_action = PPO._sample_action
-    recurrent = False
-
-    def __init__(self, model, device):
-        self.model = model
-        self.device = device
-
-
 def _head_split(model, device):
-    """How the loss of the stored rows runs behind ``model``:
+    """How the loss of the stored rows runs behind ``model`` (``_policy_split.softmax_policy`` /
+    ``gaussian_policy``):
 
       ("softmax", logits_fn, None)     ``Sequential(body..., Linear(K, A <= 31), SoftmaxCategoricalHead())``
       ("gaussian", mean_fn, scale_fn)  ``Sequential(..., Linear(., A <= 32), head)`` with a
                                        state-independent or fixed covariance
-      None                             anything else: torch.distributions on the batched forward
-
-    by the splits PPO uses (``_ActGraph._split`` / ``_gaussian_split``), on the model dressed as the
-    policy branch of the shape they recognise; the value branch they expect next to it is a
-    placeholder that is never evaluated (a ``meta`` Linear: no memory, no draw from a generator)."""
-    from pfrl_amd.nn import Branched
-    from pfrl_amd.policies import SoftmaxCategoricalHead
-
-    nn = torch.nn
-    if type(model) is not nn.Sequential or len(model) < 2:
-        return None
-    kids = list(model)
-    if (len(kids) >= 3 and type(kids[-1]) is SoftmaxCategoricalHead and isinstance(kids[-2], nn.Linear)):
-        dressed = nn.Sequential(*kids[:-2], Branched(
-            nn.Sequential(kids[-2], kids[-1]), nn.Linear(kids[-2].in_features, 1, device="meta")))
-        found = _ActGraph(_PolicyOnly(dressed, device))._split()
-        if found is not None and all(p.dtype == torch.float32 for p in model.parameters()):
-            body, pol, _ = found
-            return "softmax", (lambda x: pol(body(x))), None
-        return None
-    graph = _ActGraph(_PolicyOnly(Branched(model, nn.Identity()), device))
-    found = graph._gaussian_split()
-    if found is None:
-        return None
-    view, head = found
-    A = kids[-2].out_features
-    return "gaussian", view.child_modules[0], (lambda: graph.gaussian_scale(head, A))
+      None                             anything else: torch.distributions on the batched forward"""
+    found = _policy_split.softmax_policy(model)
+    if found is not None:
+        body, pol = found
+        return "softmax", (lambda x: pol(body(x))), None
+    found = _policy_split.gaussian_policy(model, device)
+    if found is not None:
+        return "gaussian", found.view, found.scale
+    return None
 
 
 class REINFORCE(agent.AttributeSavingMixin, agent.Agent):

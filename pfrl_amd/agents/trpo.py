@@ -12,7 +12,7 @@ With a GPU and a feed-forward model it keeps the rollout where PPO keeps it (``a
 columns, captured acting step, value pass, ``pfrl_gae_scan``) and runs the policy update without the
 host reads the reference ends every small step with:
 
-  gain / KL / entropy   pfrl_trpo_gaussian_eval behind the head-less policy (``_gaussian_split``), once
+  gain / KL / entropy   pfrl_trpo_gaussian_eval behind the head-less policy (``_policy_split``), once
                         with the gradient of the gain and once per line-search trial; any other
                         policy keeps the torch.distributions expressions
   Fisher-vector product the reference's double backward through autograd, unchanged
@@ -37,7 +37,8 @@ import torch.nn.functional as F
 
 from pfrl_amd import ops
 from pfrl_amd.agents.dqn import _mean_or_nan
-from pfrl_amd.agents.ppo import PPO, _ActGraph, _iter_minibatch_positions
+from pfrl_amd.agents import _policy_split
+from pfrl_amd.agents.ppo import PPO, _iter_minibatch_positions
 from pfrl_amd.agents.ppo_host import (HostRollouts, _actions, _states, _yield_minibatches,
                                       _yield_subset_of_sequences_with_fixed_number_of_items)
 from pfrl_amd.utils.batch_states import batch_states
@@ -344,30 +345,32 @@ class TRPO(PPO):
         write(0.0)
 
     # -- the device route ---------------------------------------------------------------------------
-    def _gaussian_policy_split(self):
-        """(head-less policy, head) when gain / KL / entropy can run as pfrl_trpo_gaussian_eval: the
-        policy ends in ``Linear(., A <= 32)`` + a Gaussian head whose scale does not depend on the
-        state (``_ActGraph._gaussian_split`` on ``Branched(policy, vf)``)."""
+    def _gaussian_found(self):
+        """``_policy_split.gaussian_actor_critic`` of ``Branched(policy, vf)`` when gain / KL / entropy
+        can run as pfrl_trpo_gaussian_eval: the policy ends in ``Linear(., A <= 32)`` + a Gaussian
+        head whose scale does not depend on the state."""
         if not self.fused_gaussian_eval or self.device.type != "cuda":
             return None
-        if self._act_graph is None:
-            self._act_graph = _ActGraph(self)
-        split = self._act_graph._gaussian_split()
-        if split is None:
-            return None
-        view, head = split
-        return view.child_modules[0], head
+        hit = self.__dict__.get("_policy_split_cache")
+        if hit is None or hit[0] is not self.model:
+            hit = self._policy_split_cache = (
+                self.model, _policy_split.gaussian_actor_critic(self.model, self.device))
+        return hit[1]
 
-    def _policy_step_fused(self, split, states, actions, advs, log_prob_old):
+    def _gaussian_policy_split(self):
+        """(head-less policy, head) of ``_gaussian_found()``, or None."""
+        found = self._gaussian_found()
+        return None if found is None else (found.view.child_modules[0], found.head)
+
+    def _policy_step_fused(self, found, states, actions, advs, log_prob_old):
         """The same step with the Gaussian row arithmetic in pfrl_trpo_gaussian_eval: once with the
         gradient of the gain (backpropagated through the head-less policy by autograd), once per
         line-search trial without.  The KL whose double backward is the Fisher-vector product is
         the reference's expression on the head's own distribution."""
-        body, head = split
+        body, head, scale_of = found.view.child_modules[0], found.head, found.scale
         params = list(self.policy.parameters())
-        A = actions.shape[1]
         mean = body(states)
-        scale = self._act_graph.gaussian_scale(head, A)
+        scale = scale_of()
         mean_old, scale_old = mean.detach(), scale.detach().contiguous()
         out0, dmean, dscale = ops.trpo_gaussian_eval(mean, scale, mean_old, scale_old, actions, advs,
                                                      log_prob_old, self.entropy_coef, want_grad=True)
@@ -382,18 +385,17 @@ class TRPO(PPO):
 
         def trial():
             with torch.no_grad(), evaluating(self.policy):
-                out = ops.trpo_gaussian_eval(body(states), self._act_graph.gaussian_scale(head, A),
-                                             mean_old, scale_old, actions, advs, log_prob_old,
-                                             self.entropy_coef)
+                out = ops.trpo_gaussian_eval(body(states), scale_of(), mean_old, scale_old, actions,
+                                             advs, log_prob_old, self.entropy_coef)
                 return torch.stack([out[0], out[1], out0[0]])
 
         self._line_search(params, full_step, trial)
 
     def _update_policy_device(self, states, actions, advs, log_prob_old):
-        split = (self._gaussian_policy_split()
+        found = (self._gaussian_found()
                  if actions.dtype == torch.float32 and actions.dim() == 2 else None)
-        if split is not None:
-            self._policy_step_fused(split, states, actions, advs, log_prob_old)
+        if found is not None:
+            self._policy_step_fused(found, states, actions, advs, log_prob_old)
         else:
             self._policy_step_by_distributions(lambda: self.policy(states), actions, advs,
                                                log_prob_old)

@@ -392,3 +392,76 @@ def test_save_load_round_trip_and_the_next_update(tmp_path):
         a.update()
     assert np.array_equal(_flat(other), _flat(ag))
     assert all(torch.equal(x, y) for x, y in zip(ag._last_losses, other._last_losses))
+
+
+# ================================================================== PPO's acting switch is PPO's
+def _tiny_a2c_update():
+    """obs 11, 4 actions, 2 envs, 3 steps: one update on loaded storage.  -> the parameters after it."""
+    import pfrl_amd as pfrl
+    from pfrl_amd import agents
+    from pfrl_amd.policies import SoftmaxCategoricalHead
+
+    obs, n_actions, n_env, steps = 11, 4, 2, 3
+    torch.manual_seed(21)
+    model = torch.nn.Sequential(
+        torch.nn.Linear(obs, 16), torch.nn.Tanh(),
+        pfrl.nn.Branched(torch.nn.Sequential(torch.nn.Linear(16, n_actions), SoftmaxCategoricalHead()),
+                         torch.nn.Linear(16, 1)))
+    ag = agents.A2C(model, torch.optim.SGD(model.parameters(), lr=1e-2), gamma=0.99, num_processes=n_env,
+                    gpu=0, update_steps=steps)
+    g = torch.Generator().manual_seed(22)
+    table = torch.randn((steps + 1) * n_env, obs, generator=g).to(ag.device)
+    actions = torch.randint(0, n_actions, (steps, n_env), generator=g)
+    ag._flush_storage(n_env, 1, actions[0])
+    ag.refs = torch.arange((steps + 1) * n_env, dtype=torch.int32, device=ag.device).view(steps + 1, n_env, 1)
+    ag._gather = lambda refs, _t=table: _t[refs.reshape(-1).long()]
+    ag.actions = actions.float().to(ag.device)
+    ag.rewards = torch.randn(steps, n_env, generator=g).to(ag.device)
+    ag.masks = torch.ones(steps, n_env).to(ag.device)
+    ag.value_preds = torch.randn(steps + 1, n_env, generator=g).to(ag.device)
+    assert ag._head_split() is not None and ag._head_split()[0] == "softmax"
+    ag.update()
+    return [p.detach().clone() for p in ag.model.parameters()]
+
+
+def _tiny_reinforce_update():
+    """obs 11, 4 actions, one episode of 3 steps through ``act`` / ``observe``, ``batchsize=1``: the
+    update runs when the episode ends.  -> the parameters after it."""
+    from pfrl_amd import agents
+    from pfrl_amd.policies import SoftmaxCategoricalHead
+
+    obs, n_actions, steps = 11, 4, 3
+    torch.manual_seed(23)
+    model = torch.nn.Sequential(torch.nn.Linear(obs, 16), torch.nn.Tanh(), torch.nn.Linear(16, n_actions),
+                                SoftmaxCategoricalHead())
+    before = [p.detach().clone() for p in model.parameters()]
+    ag = agents.REINFORCE(model, torch.optim.SGD(model.parameters(), lr=1e-2), gpu=0, beta=0.01, batchsize=1)
+    rs = np.random.RandomState(24)
+    for t in range(steps):
+        ag.act(rs.randn(obs).astype(np.float32))
+        ag.observe(rs.randn(obs).astype(np.float32), float(rs.randn()), t == steps - 1, False)
+    assert ag.device_route and ag._split[1] is not None and ag._split[1][0] == "softmax"
+    after = [p.detach().clone() for p in ag.model.parameters()]
+    assert any(not torch.equal(a, b.to(a.device)) for a, b in zip(after, before))
+    return after
+
+
+@gpu
+def test_ppo_acting_switch_does_not_reach_a2c_or_reinforce(monkeypatch, recorder):
+    """``PFRL_PPO_ACT_HEAD=0`` switches PPO's fused acting head off and nothing else: with it set, a
+    softmax A2C agent and a softmax REINFORCE agent still find their split, run their fused loss launch
+    and end one update with the parameters, bit for bit, of the same update without the variable."""
+    runs = {}
+    for value in (None, "0"):
+        if value is None:
+            monkeypatch.delenv("PFRL_PPO_ACT_HEAD", raising=False)
+        else:
+            monkeypatch.setenv("PFRL_PPO_ACT_HEAD", value)
+        calls = [recorder.count("pfrl_a2c_loss"), recorder.count("pfrl_reinforce_loss")]
+        runs[value] = (_tiny_a2c_update(), _tiny_reinforce_update())
+        assert [recorder.count("pfrl_a2c_loss") - calls[0],
+                recorder.count("pfrl_reinforce_loss") - calls[1]] == [1, 1]
+    for plain, switched in zip(runs[None], runs["0"]):
+        assert len(plain) == len(switched) > 0
+        for a, b in zip(plain, switched):
+            assert bool(torch.isfinite(b).all()) and torch.equal(a, b)
