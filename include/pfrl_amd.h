@@ -816,6 +816,29 @@ int pfrl_linear_small_fwd(const float *x, const float *w, const float *bias, flo
 int pfrl_dqn_act_head(const float *h, const float *w, const float *bias, const int32_t *choice,
                       float *q, int64_t *greedy, int64_t *action, int32_t M, int32_t K, int32_t N,
                       void *stream);
+/* The same head with Boltzmann exploration behind it, one launch (pfrl/agents/dqn.py:490-507 with
+ * `explorers.Boltzmann`, pfrl/explorers/boltzmann.py:18-26: per env softmax(q / T) and one
+ * `np.random.choice(arange(N), p=probs)`).  q as above (bit-identical to pfrl_linear_small_fwd;
+ * written unless NULL).  `u` f64 [M]: the host's draws, np.random.random_sample(M) -- choice
+ * consumes exactly one per call; `temperature`: ONE f32 in device memory (an annealed T needs no
+ * new capture).  Per row, in one lane, every step one rounded IEEE operation in this order:
+ *   z_n = q_n / T (f32),  mx = max z,  e_n = expf(z_n - mx),  s = ((e_0 + e_1) + ..) (f32),
+ *   p_n = e_n / s  (written to `probs` f32 [M,N] unless NULL);
+ *   in f64: c_n = c_(n-1) + (double)p_n,  c_n /= c_(N-1),  action = #{n : c_n <= u}
+ * (np.cumsum, the normalisation and searchsorted(side="right") of choice; at most N - 1 because
+ * c_(N-1) == 1 > u).  A row whose probabilities contain a NaN writes action = -1 and ORs 1 into
+ * `status` (i32 [1], never cleared here) with a vector atomic: the reference raises
+ * ValueError("probabilities contain NaN") there. */
+int pfrl_dqn_act_head_boltzmann(const float *h, const float *w, const float *bias, const double *u,
+                                const float *temperature, float *q, float *probs, int64_t *action,
+                                int32_t *status, int32_t M, int32_t K, int32_t N, void *stream);
+/* The same row arithmetic (one __device__ function, csrc/boltzmann_row.h: same probs and action
+ * bits for the same q row) from ready action values q f32 [M,A], 1 <= A <= 64, for models whose
+ * head the fused launch does not take (dueling heads, A > 16; pfrl/explorers/boltzmann.py:18-26,
+ * pfrl/agents/dqn.py:490-507).  A > 64, A < 1, M < 0 or a null argument other than `probs`:
+ * PFRL_ERR_ARG, nothing written.  M == 0 writes nothing. */
+int pfrl_boltzmann_select(const float *q, const double *u, const float *temperature, float *probs,
+                          int64_t *action, int32_t *status, int64_t M, int32_t A, void *stream);
 /* Forward tile programs (pfrl_conv2d_nhwc_fwd, pfrl_conv2d_u8nhwc4_fwd) planned for a batch of
  * `images` images when a call brings fewer (0: off; per host thread).  No tile program mixes rows,
  * so a row evaluated in a small batch under this plan has bit for bit the value it has inside the

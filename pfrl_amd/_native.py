@@ -225,6 +225,8 @@ EXPORTS = {
     "pfrl_linear_small_fwd": (ctypes.c_int, "ppppiiip"),
     "pfrl_linear_small_bwd": (ctypes.c_int, "ppppppiiip"),
     "pfrl_dqn_act_head": (ctypes.c_int, "pppppppiiip"),
+    "pfrl_dqn_act_head_boltzmann": (ctypes.c_int, "pppppppppiiip"),
+    "pfrl_boltzmann_select": (ctypes.c_int, "ppppppqip"),
     "pfrl_qnet_plan_images": (ctypes.c_int, "i"),
     "pfrl_squashed_gaussian_fwd": (ctypes.c_int, "pqpqppppiip"),
     "pfrl_squashed_gaussian_bwd": (ctypes.c_int, "pppppqppiip"),

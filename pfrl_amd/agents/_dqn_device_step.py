@@ -19,6 +19,17 @@ steps) and the GPU queue stays full.  Order of appends, NumPy draws, target sync
 the reference's (tests/test_host_plan.py: stream position after every call;
 tests/test_bench_path_parity.py, tests/test_agent_parity.py: whole traces).
 
+A second explorer kind takes the same step: ``explorers.Boltzmann`` (reference
+pfrl/explorers/boltzmann.py:18-26).  Its ``np.random.choice(arange(A), p=probs)`` consumes exactly
+one ``random_sample()`` per env whatever the probabilities are, so the host draws the N uniforms
+up front (``np.random.random_sample(N)``: the same stream positions), the staging slot carries
+``refs | u (f64, 16-byte aligned) | T (f32)`` and softmax, cdf and search run behind the Q head
+(``pfrl_dqn_act_head_boltzmann``; ``pfrl_boltzmann_select`` for heads the split does not take).
+``choice`` raises ``ValueError("probabilities contain NaN")`` on the spot; here the launch raises
+a status word that is copied into pinned memory behind it and looked at when that step's event is
+waited for in the run-ahead loop -- the same ``ValueError``, at most ``RUN_AHEAD`` steps late, at
+the latest on ``stop_episode``, ``save`` and ``get_statistics`` (:func:`check_pending`).
+
 Everything here is a fast path with the general code behind it: any condition that does not
 hold (another explorer, a host env, prioritized or n-step replay, recurrent model, the dense
 ``sample_n_k`` regime of a tiny buffer) falls back to ``DQN``'s own methods.
@@ -100,9 +111,98 @@ def act_split(agent):
     return out
 
 
+EPS_GREEDY, BOLTZMANN = "eps_greedy", "boltzmann"      # the explorer kinds of the device step
+MAX_BOLTZMANN_ACTIONS = 64                             # (kMaxBoltzmannA of csrc/boltzmann_row.h)
+
+
+def boltzmann_temperature(ex):
+    """``ex.T`` as the float32 the kernels divide by when ``ex`` is exactly ``explorers.Boltzmann``
+    with its own ``select_action`` and a positive finite temperature (also as float32); else None."""
+    from pfrl_amd.explorers.boltzmann import Boltzmann
+
+    if type(ex) is not Boltzmann or "select_action" in vars(ex):
+        return None
+    T = ex.T
+    if isinstance(T, bool) or not isinstance(T, (int, float, np.integer, np.floating)):
+        return None
+    with np.errstate(over="ignore"):
+        T = np.float32(T)
+    return T if np.isfinite(T) and T > 0 else None
+
+
+def act_kind(agent, batch_obs):
+    """The explorer kind under which :func:`act` takes this step, or None (the general code of
+    ``DQN.batch_act`` runs): training mode, a DeviceObsBatch, a non-recurrent model on CUDA and
+    either the epsilon-greedy family or plain Boltzmann."""
+    if not (agent.training and isinstance(batch_obs, DeviceObsBatch) and not agent.recurrent
+            and agent.device.type == "cuda"):
+        return None
+    if agent._explorer_draws_before_greedy():
+        return EPS_GREEDY
+    return BOLTZMANN if boltzmann_temperature(agent.explorer) is not None else None
+
+
+def boltzmann_action_values(av):
+    """The [N, A] float32 action values the Boltzmann kernels read, or None: a
+    ``DiscreteActionValue`` (what ``Boltzmann.select_action`` asserts) with 1 <= A <= 64."""
+    from pfrl_amd.action_value import DiscreteActionValue
+
+    if not isinstance(av, DiscreteActionValue):
+        return None
+    q = av.q_values
+    if not (torch.is_tensor(q) and q.dim() == 2 and q.dtype == torch.float32
+            and 1 <= q.shape[1] <= MAX_BOLTZMANN_ACTIONS):
+        return None
+    return q.detach().contiguous()
+
+
+def _boltzmann_model_ok(agent, batch_obs):
+    """Whether the model's output is one the Boltzmann launches take -- known before the host
+    draws, because a step that falls back must leave NumPy's stream to the general code.  A
+    recognised head (act_split) is; any other model is evaluated ONCE on the first batch, with
+    torch's generators restored behind it (NoisyNet layers draw), and the answer kept per model."""
+    if act_split(agent) is not None:
+        return True
+    model = agent.model
+    key = tuple(id(m) for m in model.modules())
+    hit = agent.__dict__.get("_boltzmann_model_cache")
+    if hit is not None and hit[0] is model and hit[1] == key:
+        return hit[2]
+    with torch.random.fork_rng(devices=[agent.device]), torch.no_grad(), evaluating(model):
+        ok = boltzmann_action_values(agent._evaluate_model(batch_obs)) is not None
+    batch_obs._refs_dev = None
+    agent._boltzmann_model_cache = (model, key, ok)
+    return ok
+
+
+def _wait_step(agent, step):
+    """Waits for a step's event; raises what ``np.random.choice`` raises in the reference when
+    that step's status word (Boltzmann steps only) came back set.  The device word is sticky (the
+    kernels only OR into it): it is cleared here, so that the error is reported once."""
+    ev, status = step
+    ev.synchronize()
+    if status is not None and int(status[0]) != 0:
+        status.zero_()
+        agent._act_status.zero_()
+        raise ValueError("probabilities contain NaN")
+
+
+def check_pending(agent):
+    """Looks at the status word of every Boltzmann step still in flight (module docstring)."""
+    evs = agent.__dict__.get("_step_events")
+    pending = [step for step in evs or () if step[1] is not None]
+    if pending:
+        rest = [step for step in evs if step[1] is None]
+        evs.clear()
+        evs.extend(rest)
+        for step in pending:
+            _wait_step(agent, step)
+
+
 class ActGraph:
     """The device side of ``DQN.batch_act`` on the device-step path -- observation gather, trunk,
-    Q head + argmax + epsilon-greedy decision -- as ONE captured HIP graph per batch shape, fed by
+    Q head + argmax + epsilon-greedy decision, or Q head + Boltzmann draw -- as ONE captured HIP
+    graph per batch shape and explorer kind, fed by
     the step's single staging transfer (frame slots + the host's draws) landing in the graph's own
     input block (reference pfrl/agents/dqn.py:490-507).  Two instances alternate, so the actions
     of a step stay valid while the next step's are computed.  The graph reads the frame ring and
@@ -118,13 +218,15 @@ class ActGraph:
         return (os.environ.get("PFRL_DQN_ACT_GRAPH", "1") != "0" and agent.use_graphs
                 and act_split(agent) is not None)
 
-    def _body(self, agent, batch_obs, inp, N, k, off_choice, out):
+    def _body(self, agent, batch_obs, inp, N, k, off_choice, out, kind):
         refs_bytes = 4 * N * k
         batch_obs._refs_dev = inp[:refs_bytes].view(torch.int32).view(N, k)
+        if kind == BOLTZMANN:
+            return _act_launches_boltzmann(agent, batch_obs, *_boltzmann_draws(inp, N, off_choice), out)
         choice = inp[off_choice:off_choice + 4 * N].view(torch.int32)
         return _act_launches(agent, batch_obs, choice, out)
 
-    def _capture(self, agent, batch_obs, N, k, off_choice, need):
+    def _capture(self, agent, batch_obs, N, k, off_choice, need, kind):
         from pfrl_amd.agents.graphed_update import _capturing
 
         dev = agent.device
@@ -133,38 +235,42 @@ class ActGraph:
             inp = torch.zeros(_align16(need), dtype=torch.uint8, device=dev)
             inp[:4 * N * k].view(torch.int32).copy_(
                 torch.from_numpy(np.ascontiguousarray(batch_obs.refs.reshape(-1))).to(dev))
-            inp[off_choice:off_choice + 4 * N].view(torch.int32).fill_(-1)
+            if kind == BOLTZMANN:
+                _boltzmann_draws(inp, N, off_choice)[1].fill_(1.0)    # (u = 0 at T = 1 until a step lands)
+            else:
+                inp[off_choice:off_choice + 4 * N].view(torch.int32).fill_(-1)
             out = torch.empty(N, dtype=torch.int64, device=dev)
             cur = torch.cuda.current_stream(dev)
             side = torch.cuda.Stream(dev)
             side.wait_stream(cur)
             with torch.cuda.stream(side):
                 for _ in range(2):
-                    if self._body(agent, batch_obs, inp, N, k, off_choice, out) is None:
+                    if self._body(agent, batch_obs, inp, N, k, off_choice, out, kind) is None:
                         cur.wait_stream(side)
                         return None
             cur.wait_stream(side)
             g = torch.cuda.CUDAGraph()
             with ops.profile_paused(), _capturing(g, self.pool):
-                self._body(agent, batch_obs, inp, N, k, off_choice, out)
+                self._body(agent, batch_obs, inp, N, k, off_choice, out, kind)
             if self.pool is None:
                 self.pool = g.pool()
             pair.append((g, inp, out))
         return [pair, 0]
 
-    def run(self, agent, batch_obs, ring, tok, N, k, off_choice, need):
+    def run(self, agent, batch_obs, ring, tok, N, k, off_choice, need, kind=EPS_GREEDY):
         """Ships pinned slot ``tok`` into the graph's input block and replays; returns the
         actions (int64 [N], owned by the graph instance) or None when the model cannot take the
-        fused head (the caller then commits the slot to the ring and launches eagerly)."""
+        fused head (the caller then commits the slot to the ring and launches eagerly).  The
+        explorer kind is part of the key: another explorer on a live agent is another graph."""
         model = agent.model
         fr = batch_obs.store
         key = (N, k, id(model), tuple(id(m) for m in model.modules()), id(fr),
-               getattr(fr, "emit_channels_last", None), id(agent.phi))
+               getattr(fr, "emit_channels_last", None), id(agent.phi), kind)
         e = self.entries.get(key)
         if e is None:
             if len(self.entries) > 8:
                 self.entries.clear()
-            e = self.entries[key] = self._capture(agent, batch_obs, N, k, off_choice, need) or False
+            e = self.entries[key] = self._capture(agent, batch_obs, N, k, off_choice, need, kind) or False
         if e is False:
             return None
         pair, at = e
@@ -196,46 +302,105 @@ def _act_launches(agent, batch_obs, choice, out=None):
         return ops.dqn_act_head(h, lin.weight, lin.bias, choice, out=out)[0]
 
 
+def _boltzmann_draws(block, N, off):
+    """(u f64 [N], T f32 [1]) of a staging block, host array or device tensor alike."""
+    f64, f32 = (np.float64, np.float32) if isinstance(block, np.ndarray) else (torch.float64, torch.float32)
+    return block[off:off + 8 * N].view(f64), block[off + 8 * N:off + 8 * N + 4].view(f32)
+
+
+def _act_launches_boltzmann(agent, batch_obs, u, temperature, out=None):
+    """gather -> trunk -> fused head with the Boltzmann draw behind it, or model -> q_values ->
+    pfrl_boltzmann_select for a head the split does not take: the actions (int64 [N]), or None
+    when a capture (``out``) meets hidden activations pfrl_dqn_act_head_boltzmann does not read."""
+    split = act_split(agent)
+    status = agent._act_status
+    with torch.no_grad(), evaluating(agent.model):
+        if split is None:
+            av = agent._evaluate_model(batch_obs)
+        else:
+            body, lin = split
+            agent._route_observation_layout(batch_obs)
+            h = body(agent.batch_states(batch_obs, agent.device, agent.phi))
+            if (torch.is_tensor(h) and h.dim() == 2 and h.dtype == torch.float32 and h.is_contiguous()
+                    and h.shape[1] == lin.in_features):
+                return ops.dqn_act_head_boltzmann(h, lin.weight, lin.bias, u, temperature, status,
+                                                  out=out)[0]
+            if out is not None:
+                return None
+            av = list(agent.model._modules.values())[-1](lin(h))
+        q = boltzmann_action_values(av)
+        if q is None:
+            raise RuntimeError("pfrl_amd: the model's action values changed kind under Boltzmann "
+                               "exploration on the device step")
+        return ops.boltzmann_select(q, u, temperature, status, out=out)[0]
+
+
 def act(agent, batch_obs):
-    """``DQN.batch_act`` in training mode for a DeviceObsBatch; None = conditions not met."""
-    if not (agent.training and isinstance(batch_obs, DeviceObsBatch) and not agent.recurrent
-            and agent.device.type == "cuda" and agent._explorer_draws_before_greedy()):
+    """``DQN.batch_act`` in training mode for a DeviceObsBatch; None = conditions not met.  A
+    Boltzmann step whose probabilities hold a NaN raises the reference's ``ValueError`` up to
+    ``RUN_AHEAD`` steps late (module docstring)."""
+    kind = act_kind(agent, batch_obs)
+    if kind is None:
         return None
     ex = agent.explorer
-    n_act = host_plan.recognise_randint(ex.random_action_func)
-    if n_act is None or ex.logger.isEnabledFor(logging.DEBUG):
-        return None
     N, k = batch_obs.refs.shape
     refs_bytes = 4 * N * k
     off_choice = _align16(refs_bytes)
-    need = off_choice + 4 * N
+    if kind == EPS_GREEDY:
+        n_act = host_plan.recognise_randint(ex.random_action_func)
+        if n_act is None or ex.logger.isEnabledFor(logging.DEBUG):
+            return None
+        need = off_choice + 4 * N
+    else:
+        if not _boltzmann_model_ok(agent, batch_obs):
+            return None
+        need = off_choice + 8 * N + 4           # refs | u (f64, 16-byte aligned) | T (f32)
+        if "_act_status" not in agent.__dict__:
+            agent._act_status = torch.zeros(1, dtype=torch.int32, device=agent.device)
+            agent._act_status_host = torch.zeros(2 * RUN_AHEAD, dtype=torch.int32).pin_memory()
+            agent._act_status_at = 0
     ring = agent.__dict__.get("_act_ring")
     if ring is None or ring.slot_bytes < need:
+        check_pending(agent)
         ring = agent._act_ring = StagingRing(agent.device, slot_bytes=max(1 << 14, need + 64),
                                              n_slots=2 * RUN_AHEAD + 2)
         agent._step_events = collections.deque()
     # bounded run-ahead: wait for the step RUN_AHEAD steps back
     evs = agent._step_events
     while len(evs) >= RUN_AHEAD:
-        evs.popleft().synchronize()
+        _wait_step(agent, evs.popleft())
     host, tok = ring.reserve()
     host[:refs_bytes].view(np.int32)[:] = batch_obs.refs.reshape(-1)
-    choice = host[off_choice:need].view(np.int32)
-    ex.epsilon = eps = ex.compute_epsilon(agent.t)
-    host_plan.eps_greedy(N, eps, n_act, out=choice)
+    if kind == EPS_GREEDY:
+        choice = host[off_choice:need].view(np.int32)
+        ex.epsilon = eps = ex.compute_epsilon(agent.t)
+        host_plan.eps_greedy(N, eps, n_act, out=choice)
+    else:
+        u, temperature = _boltzmann_draws(host, N, off_choice)
+        u[:] = np.random.random_sample(N)       # env order: the positions of N scalar choice() calls
+        temperature[0] = boltzmann_temperature(ex)
     actions = None
     if ActGraph.applicable(agent):
         graph = agent.__dict__.get("_act_graph")
         if graph is None:
             graph = agent._act_graph = ActGraph(agent)
-        actions = graph.run(agent, batch_obs, ring, tok, N, k, off_choice, need)
+        actions = graph.run(agent, batch_obs, ring, tok, N, k, off_choice, need, kind)
     if actions is None:
         dev = ring.commit(tok, need)
         batch_obs._refs_dev = dev[:refs_bytes].view(torch.int32).view(N, k)
-        actions = _act_launches(agent, batch_obs, dev[off_choice:need].view(torch.int32))
+        if kind == EPS_GREEDY:
+            actions = _act_launches(agent, batch_obs, dev[off_choice:need].view(torch.int32))
+        else:
+            actions = _act_launches_boltzmann(agent, batch_obs, *_boltzmann_draws(dev, N, off_choice))
+    status = None
+    if kind == BOLTZMANN:
+        at = agent._act_status_at
+        agent._act_status_at = (at + 1) % (2 * RUN_AHEAD)
+        status = agent._act_status_host[at:at + 1]
+        status.copy_(agent._act_status, non_blocking=True)
     ev = torch.cuda.Event()
     ev.record()
-    evs.append(ev)
+    evs.append((ev, status))
     agent._last_obs_batch = batch_obs
     agent._last_actions_dev = actions
     agent.batch_last_obs = LastBatch(batch_obs)

@@ -1122,11 +1122,26 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
             return False
         return not self.recurrent or self.replay_buffer.n_episodes >= self.minibatch_size
 
+    def _check_device_steps(self):
+        """A Boltzmann step of the device path reports NaN probabilities through a status word
+        that is read when the step is waited for (agents/_dqn_device_step.py); steps still in
+        flight are looked at here, so that the reference's ``ValueError`` is raised at the latest
+        on ``stop_episode``, ``save`` and ``get_statistics``."""
+        if self.__dict__.get("_step_events"):
+            from pfrl_amd.agents import _dqn_device_step
+
+            _dqn_device_step.check_pending(self)
+
     def stop_episode(self):
+        self._check_device_steps()
         if self.recurrent:
             self.test_recurrent_states = None
 
     # -- persistence / statistics ----------------------------------------------
+    def save(self, dirname):
+        self._check_device_steps()
+        super().save(dirname)
+
     def save_snapshot(self, dirname):
         self.save(dirname)
         torch.save(self.t, os.path.join(dirname, "t.pt"))
@@ -1142,6 +1157,7 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
         self.replay_buffer.load(os.path.join(dirname, "replay_buffer.pkl"))
 
     def get_statistics(self):
+        self._check_device_steps()
         return [
             ("average_q", _mean_or_nan(self.q_record.values())),
             ("average_loss", _mean_or_nan(self.loss_record.values())),

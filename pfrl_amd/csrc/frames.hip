@@ -9,6 +9,7 @@
 // instruction of a wave covers 1 KiB of contiguous HBM.
 #include <hip/hip_ext.h>
 
+#include "boltzmann_row.h"
 #include "common.h"
 #include "nhwc.h"
 
@@ -241,6 +242,47 @@ extern "C" int pfrl_select_actions(const void *greedy, int greedy_is_i32, const 
     else
         hipLaunchKernelGGL(k_select_actions<int64_t>, grid, block, 0, (hipStream_t)stream,
                            (const int64_t *)greedy, choice, out, n);
+    PFRL_LAUNCH_CHECK();
+}
+
+// Boltzmann exploration on the device from ready action values (see pfrl_boltzmann_select in
+// include/pfrl_amd.h): one lane per row, 64 rows per workgroup.  The workgroup's rows are one
+// contiguous piece of q: it is staged into LDS with coalesced loads (row stride 65 floats, so that
+// the 64 lanes walking their rows hit 32 different banks), each lane runs boltzmann_row over its
+// row in place, and the probabilities leave the same way.
+constexpr int kBoltzmannRows = 64;
+
+__global__ __launch_bounds__(kBoltzmannRows) void k_boltzmann_select(
+    const float *__restrict__ q, const double *__restrict__ u, const float *__restrict__ temperature,
+    float *__restrict__ probs, int64_t *__restrict__ action, int32_t *__restrict__ status,
+    const int64_t M, const int A) {
+    __shared__ float rows[kBoltzmannRows][kMaxBoltzmannA + 1];
+    const int tid = threadIdx.x;
+    const int64_t m0 = (int64_t)blockIdx.x * kBoltzmannRows, m = m0 + tid;
+    const int here = (int)(M - m0 < kBoltzmannRows ? M - m0 : kBoltzmannRows);
+    const double um = m < M ? u[m] : 0.0;
+    const float T = temperature[0];
+    for (int i = tid; i < here * A; i += kBoltzmannRows) rows[i / A][i % A] = q[m0 * A + i];
+    __syncthreads();
+    if (m < M) {
+        const int64_t a = boltzmann_row(rows[tid], A, T, um);
+        action[m] = a;
+        if (a < 0) atomicOr(status, 1);
+    }
+    if (probs == nullptr) return;
+    __syncthreads();
+    for (int i = tid; i < here * A; i += kBoltzmannRows) probs[m0 * A + i] = rows[i / A][i % A];
+}
+
+extern "C" int pfrl_boltzmann_select(const float *q, const double *u, const float *temperature,
+                                     float *probs, int64_t *action, int32_t *status, int64_t M,
+                                     int32_t A, void *stream) {
+    PFRL_CHECK_ARG(q && u && temperature && action && status, "pfrl_boltzmann_select: null argument");
+    PFRL_CHECK_ARG(A >= 1 && A <= kMaxBoltzmannA && M >= 0, "pfrl_boltzmann_select: 1 <= A <= 64, M >= 0");
+    if (M == 0) return 0;
+    hipLaunchKernelGGL(k_boltzmann_select, dim3((unsigned)((M + kBoltzmannRows - 1) / kBoltzmannRows)),
+                       dim3(kBoltzmannRows), 0, (hipStream_t)stream, q, u, temperature, probs, action,
+                       status, M, A);
     PFRL_LAUNCH_CHECK();
 }
 

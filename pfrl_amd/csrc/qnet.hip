@@ -30,6 +30,7 @@
 // (partials + one multi-tensor reduce) where the output is small.
 #include <type_traits>
 
+#include "boltzmann_row.h"
 #include "common.h"
 #include "rms_update.h"
 
@@ -1958,6 +1959,38 @@ __global__ __launch_bounds__(256) void k_dqn_act_head(const float *__restrict__ 
     }
 }
 
+// The same head with Boltzmann exploration behind it (see pfrl_dqn_act_head_boltzmann in
+// include/pfrl_amd.h): the action values are those of k_linear_small_fwd bit for bit, the row
+// arithmetic is boltzmann_row's, in lane 0.
+template <int N>
+__global__ __launch_bounds__(256) void k_dqn_act_head_boltzmann(
+    const float *__restrict__ h, const float *__restrict__ w, const float *__restrict__ bias,
+    const double *__restrict__ u, const float *__restrict__ temperature, float *__restrict__ q,
+    float *__restrict__ probs, int64_t *__restrict__ action, int32_t *__restrict__ status, int K) {
+    __shared__ float part[4][N];
+    __shared__ float qrow[N];
+    const int m = blockIdx.x, tid = threadIdx.x;
+    // (requested before the row product: nothing below waits for them until the very end)
+    const double um = tid == 0 ? u[m] : 0.0;
+    const float T = tid == 0 ? temperature[0] : 1.f;
+    float v = small_fwd_row<N>(h, w, K, m, part);
+    if (tid < N) {
+        if (bias != nullptr) v += bias[tid];
+        qrow[tid] = v;
+        if (q != nullptr) q[(size_t)m * N + tid] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int64_t a = boltzmann_row(qrow, N, T, um);
+        action[m] = a;
+        if (a < 0) atomicOr(status, 1);
+        if (probs != nullptr) {
+#pragma unroll
+            for (int n = 0; n < N; ++n) probs[(size_t)m * N + n] = qrow[n];
+        }
+    }
+}
+
 // dx[m][k] = sum_n dy[m][n] w[n][k];  dw[n][k] = sum_m dy[m][n] x[m][k];  db[n] = sum_m dy[m][n]
 // One launch, two kinds of workgroup.  The first ceil(K / 32) own dw (and db): 32 k columns
 // x 8 slices of the batch per workgroup, each thread walks its rows m = slice, slice + 8, ..
@@ -2827,6 +2860,22 @@ extern "C" int pfrl_dqn_act_head(const float *h, const float *w, const float *bi
                        choice, q, greedy, action, K)
     SMALL_DISPATCH(N, CALL_ACT)
 #undef CALL_ACT
+    PFRL_LAUNCH_CHECK();
+}
+
+extern "C" int pfrl_dqn_act_head_boltzmann(const float *h, const float *w, const float *bias,
+                                           const double *u, const float *temperature, float *q,
+                                           float *probs, int64_t *action, int32_t *status, int32_t M,
+                                           int32_t K, int32_t N, void *stream) {
+    PFRL_CHECK_ARG(N >= 1 && N <= SMALL_N && M >= 1 && K >= 1,
+                   "pfrl_dqn_act_head_boltzmann: 1 <= N <= 16");
+    PFRL_CHECK_ARG(h && w && u && temperature && action && status,
+                   "pfrl_dqn_act_head_boltzmann: null argument");
+#define CALL_BOLTZMANN(NN)                                                                          \
+    hipLaunchKernelGGL(k_dqn_act_head_boltzmann<NN>, dim3(M), dim3(256), 0, (hipStream_t)stream, h, \
+                       w, bias, u, temperature, q, probs, action, status, K)
+    SMALL_DISPATCH(N, CALL_BOLTZMANN)
+#undef CALL_BOLTZMANN
     PFRL_LAUNCH_CHECK();
 }
 

@@ -86,6 +86,48 @@ def dqn_act_head(h, weight, bias, choice=None, want_q=False, out=None):
     return out, q
 
 
+def _boltzmann_args(M, u, temperature, status, dev, want_probs, A, out):
+    assert u.dtype == torch.float64 and u.numel() == M and u.data_ptr() % 8 == 0
+    assert temperature.dtype == torch.float32 and temperature.numel() == 1
+    assert status.dtype == torch.int32 and status.numel() == 1
+    if out is None:
+        out = torch.empty(M, dtype=torch.int64, device=dev)
+    assert out.dtype == torch.int64 and out.numel() == M
+    probs = torch.empty((M, A), dtype=torch.float32, device=dev) if want_probs else None
+    return out, probs
+
+
+def dqn_act_head_boltzmann(h, weight, bias, u, temperature, status, want_q=False, want_probs=False,
+                           out=None):
+    """The narrow Q head of the acting path with Boltzmann exploration in one launch
+    (pfrl_dqn_act_head_boltzmann; reference pfrl/agents/dqn.py:490-507 with
+    pfrl/explorers/boltzmann.py:18-26): ``h`` [M, K] f32, ``weight`` [A <= 16, K], ``u`` f64 [M]
+    (``np.random.random_sample(M)``), ``temperature`` ONE f32 and ``status`` ONE int32 on the
+    device.  Returns (actions int64 [M], q or None, probs or None); a row whose probabilities hold
+    a NaN gets action -1 and sets ``status``."""
+    M, K = h.shape
+    A = weight.shape[0]
+    assert h.dtype == torch.float32 and h.is_contiguous() and weight.is_contiguous() and 1 <= A <= 16
+    out, probs = _boltzmann_args(M, u, temperature, status, h.device, want_probs, A, out)
+    q = torch.empty((M, A), dtype=torch.float32, device=h.device) if want_q else None
+    check(_native.lib().pfrl_dqn_act_head_boltzmann(
+        _ptr(h), _ptr(weight), _ptr(bias), _ptr(u), _ptr(temperature), _ptr(q), _ptr(probs), _ptr(out),
+        _ptr(status), M, K, A, _stream()), "dqn_act_head_boltzmann")
+    return out, q, probs
+
+
+def boltzmann_select(q, u, temperature, status, want_probs=False, out=None):
+    """Boltzmann exploration from ready action values ``q`` f32 [M, A <= 64]
+    (pfrl_boltzmann_select): the row arithmetic and the arguments of
+    :func:`dqn_act_head_boltzmann`.  Returns (actions int64 [M], probs or None)."""
+    M, A = q.shape
+    assert q.dtype == torch.float32
+    out, probs = _boltzmann_args(M, u, temperature, status, q.device, want_probs, A, out)
+    check(_native.lib().pfrl_boltzmann_select(_ptr(q), _ptr(u), _ptr(temperature), _ptr(probs), _ptr(out),
+                                              _ptr(status), M, A, _stream()), "boltzmann_select")
+    return out, probs
+
+
 def _spatial_hw(fshape):
     """(H, W) if the frame is one 2-D plane ((H, W) or (1, H, W)), else None."""
     dims = [d for d in fshape]
