@@ -919,6 +919,34 @@ int pfrl_squashed_head_fwd(const float *x, int64_t ldx, float clamp_lo, float cl
 int pfrl_squashed_head_bwd(const float *g_action, const float *g_logp, const float *action,
                            const float *eps, const float *x, int64_t ldx, float clamp_lo, float clamp_hi,
                            int32_t mode, float *g_x, int32_t B, int32_t A, void *stream);
+/* The acting step of SAC / TD3 / DDPG (csrc/actor_act.hip): the policy's last nn.Linear -- h [M][K]
+ * the body's output, w [n_out][K], bias [n_out], all f32 row-major contiguous -- and everything behind
+ * it in one launch.  The sum over K has one fixed order that depends on K alone: a row's result is a
+ * function of that row, whatever M is and wherever the row stands.  Gates: 1 <= A <= 32,
+ * 1 <= K <= 1024, 0 <= M <= 4096; outside them, or with a NULL h / w / bias / action, PFRL_ERR_ARG
+ * before anything is launched or written.  M == 0: success, nothing written.
+ *
+ * pfrl_squashed_head_act (pfrl/agents/soft_actor_critic.py:317-334 with the head of
+ *   train_soft_actor_critic.py:128-141): x = h w^T + b [M][2A] (written to x_out unless NULL), (mean |
+ *   log_scale) = chunk(x, 2); eps [M][A] given: action = tanh(mean + eps * scale), scale, sum and tanh
+ *   by the __device__ function pfrl_squashed_head_fwd uses (csrc/squashed_row.h: the same action bits
+ *   from the same x and eps; multiply and add are two rounded operations, as `torch.normal(loc,
+ *   scale)` rounds them); eps NULL: action = tanh(mean), the distribution's mode
+ *   (`act_deterministically`).  clamp_lo / clamp_hi / mode as in pfrl_squashed_head_fwd.
+ * pfrl_deterministic_head_act (pfrl/agents/td3.py:262-281, ddpg.py:253-273 with
+ *   pfrl/explorers/additive_gaussian.py:26-36, additive_ou.py:49-66): y = h w^T + b [M][A] (y_out
+ *   unless NULL); g = tanh(y) * bound_scale + bound_shift when the two vectors [A] are given
+ *   (pfrl/nn/bound_by_tanh.py: (high - low) / 2 and (high + low) / 2, two rounded operations), else
+ *   g = y (greedy_out unless NULL); action = g when noise is NULL, else t = g + noise [M][A], t = t <
+ *   low ? low : t, t = t > high ? high : t (`np.clip`; a NaN passes through; low / high [A], -inf /
+ *   +inf for an absent side, required with noise). */
+int pfrl_squashed_head_act(const float *h, const float *w, const float *bias, float clamp_lo,
+                           float clamp_hi, int32_t mode, const float *eps, float *x_out, float *action,
+                           int32_t M, int32_t K, int32_t A, void *stream);
+int pfrl_deterministic_head_act(const float *h, const float *w, const float *bias,
+                                const float *bound_scale, const float *bound_shift, const float *noise,
+                                const float *low, const float *high, float *y_out, float *greedy_out,
+                                float *action, int32_t M, int32_t K, int32_t A, void *stream);
 int pfrl_soft_update(int32_t n_tensors, float *const *dst, const float *const *src,
                      const int64_t *numel, double tau, void *stream);
 int pfrl_adam_step(int32_t n_tensors, float *const *params, const float *const *grads,

@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libpfrl_amd.so")
 # measurement hook (tools/build_variant.sh): another build of the same sources, e.g. other compiler
 # flags, loaded instead of the in-tree library.  Never set by the package, the tests or bench.py.
 _LIB_OVERRIDE = os.environ.get("PFRL_AMD_LIB")
-SOURCES = ["frames.hip", "replay.hip", "sumtree.hip", "rollout.hip", "optim.hip", "tdloss.hip", "operator_td.hip", "bias_act.hip", "noisy.hip", "c51.hip", "iqn.hip", "dueling.hip", "qnet.hip", "actor.hip", "hostplan.hip", "philox.hip", "ppo_gaussian.hip", "trpo.hip", "reinforce.hip", "a2c.hip", "td3.hip"]
+SOURCES = ["frames.hip", "replay.hip", "sumtree.hip", "rollout.hip", "optim.hip", "tdloss.hip", "operator_td.hip", "bias_act.hip", "noisy.hip", "c51.hip", "iqn.hip", "dueling.hip", "qnet.hip", "actor.hip", "actor_act.hip", "hostplan.hip", "philox.hip", "ppo_gaussian.hip", "trpo.hip", "reinforce.hip", "a2c.hip", "td3.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     # the parity contract is one correctly rounded IEEE op per source op
@@ -232,6 +232,8 @@ EXPORTS = {
     "pfrl_squashed_gaussian_bwd": (ctypes.c_int, "pppppqppiip"),
     "pfrl_squashed_head_fwd": (ctypes.c_int, "pqffippppiip"),
     "pfrl_squashed_head_bwd": (ctypes.c_int, "pppppqffipiip"),
+    "pfrl_squashed_head_act": (ctypes.c_int, "pppffipppiiip"),
+    "pfrl_deterministic_head_act": (ctypes.c_int, "pppppppppppiiip"),
     "pfrl_soft_update": (ctypes.c_int, "ipppdp"),
     "pfrl_adam_step": (ctypes.c_int, "ippppppdddddpp"),
     "pfrl_adam_step_ex": (ctypes.c_int, "ippppppppdpdddddpp"),

@@ -3,7 +3,8 @@ pfrl_ppo_gaussian_*, pfrl_a2c_*loss, pfrl_reinforce_*loss, pfrl_trpo_gaussian_ev
 a model, for PPO, A2C, REINFORCE and TRPO.  Each returns None for a model it does not recognise, else
 views of the model without its head: same classes, same children and parameters, so a fused trunk
 stays fused and the model keeps its head.  Switches, stock-method checks and caches stay with the
-agents."""
+agents.  At the end: the two policies the acting launches of SAC, TD3 and DDPG run behind
+(pfrl_squashed_head_act, pfrl_deterministic_head_act; agents/_actor_device_step.py)."""
 import collections
 from typing import NamedTuple, Optional
 
@@ -148,3 +149,81 @@ def gaussian_policy(model, device):
     if found is None:
         return None
     return _gaussian_split(model, *found, device)
+
+
+# -------------------------------------------------------------------------------------------------
+# the continuous replay agents' acting launches (pfrl_squashed_head_act, pfrl_deterministic_head_act)
+# -------------------------------------------------------------------------------------------------
+def _act_layer_ok(lin, n_out_per_action):
+    """The last ``nn.Linear`` as the acting launches read it: float32, with a bias, contiguous,
+    inside the gates of csrc/actor_act.hip."""
+    from pfrl_amd.ops import ACTOR_ACT_MAX_A, ACTOR_ACT_MAX_K
+
+    return (isinstance(lin, nn.Linear) and lin.bias is not None and lin.weight.dtype == torch.float32
+            and lin.bias.dtype == torch.float32 and lin.weight.is_contiguous()
+            and lin.out_features % n_out_per_action == 0
+            and 1 <= lin.out_features // n_out_per_action <= ACTOR_ACT_MAX_A
+            and 1 <= lin.in_features <= ACTOR_ACT_MAX_K)
+
+
+class SquashedGaussianSplit(NamedTuple):
+    """``body``: the policy without its last layer and head, yielding h [M, K]; ``layer``: the
+    ``nn.Linear(K, 2A)``; ``spec``: the ``HeadSpec`` of the head function."""
+
+    body: nn.Module
+    layer: nn.Linear
+    spec: object
+
+
+def squashed_gaussian_policy(policy, device, spec=None):
+    """:class:`SquashedGaussianSplit` when ``policy`` is ``Sequential(body..., Linear(K, 2A),
+    Lambda(head))`` -- the reference's example (examples/mujoco/reproduction/soft_actor_critic/
+    train_soft_actor_critic.py:159-179) -- with a non-empty body, float32 parameters, A <= 32,
+    K <= 1024 and ``head`` accepted by ``utils.squashed_gaussian.recognise_head`` (probed on
+    ``device``; ``spec``: the answer of an earlier probe of this head, taken as it is)."""
+    from pfrl_amd.nn import Lambda
+    from pfrl_amd.utils import squashed_gaussian
+
+    if not isinstance(policy, nn.Sequential) or len(policy) < 3:
+        return None
+    lin, head = policy[len(policy) - 2], policy[len(policy) - 1]
+    if type(head) is not Lambda or not _act_layer_ok(lin, 2) or not _all_f32(policy):
+        return None
+    if spec is None:
+        spec = squashed_gaussian.recognise_head(head.lambd, lin.out_features, device)
+    if spec is None or 2 * spec.A != lin.out_features:
+        return None
+    return SquashedGaussianSplit(prefix_view(policy, drop=2), lin, spec)
+
+
+class DeterministicSplit(NamedTuple):
+    """``body``: the policy without its last layer and what follows, yielding h [M, K]; ``layer``:
+    the ``nn.Linear(K, A)``; ``bound``: the ``BoundByTanh`` behind it, or None."""
+
+    body: nn.Module
+    layer: nn.Linear
+    bound: Optional[nn.Module]
+
+
+def deterministic_policy(policy):
+    """:class:`DeterministicSplit` when ``policy`` is ``Sequential(body..., Linear(K, A),
+    [BoundByTanh], DeterministicHead())`` -- the reference's DDPG example (examples/mujoco/
+    reproduction/ddpg/train_ddpg.py:133-141) -- with a non-empty body, float32 parameters, a bias,
+    A <= 32 and K <= 1024.  (An ``nn.Tanh`` in place of the ``BoundByTanh``, as in the reference's
+    train_td3.py:122-130, is not taken: the agent keeps calling the policy.)"""
+    from pfrl_amd.nn import BoundByTanh
+    from pfrl_amd.policies import DeterministicHead
+
+    if not isinstance(policy, nn.Sequential) or len(policy) < 3:
+        return None
+    kids = list(policy._modules.values())
+    if type(kids[-1]) is not DeterministicHead:
+        return None
+    bound = kids[-2] if type(kids[-2]) is BoundByTanh else None
+    drop = 2 if bound is None else 3
+    if len(kids) <= drop:
+        return None
+    lin = kids[-drop]
+    if not _act_layer_ok(lin, 1) or not _all_f32(policy):
+        return None
+    return DeterministicSplit(prefix_view(policy, drop=drop), lin, bound)

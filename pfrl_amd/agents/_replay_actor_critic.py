@@ -140,10 +140,35 @@ class ReplayActorCritic(AttributeSavingMixin, BatchAgent):
         self._after_update(variant)
 
     # -- acting / observing -----------------------------------------------------------------
-    def _batch_select_actions(self, batch_obs):
+    def _batch_select_actions_eager(self, batch_obs):
         with torch.no_grad(), evaluating(self._policy()):
             xs = self.batch_states(batch_obs, self.device, self.phi)
             return self._policy()(xs).sample().cpu().numpy()
+
+    def _batch_select_actions(self, batch_obs):
+        # one staging transfer + one captured graph with the fused head launch where the policy is
+        # recognised (agents/_actor_device_step.py); None: the policy is called as it is
+        from pfrl_amd.agents import _actor_device_step
+
+        actions = _actor_device_step.deterministic_act(self, batch_obs, explore=False)
+        if actions is None:
+            actions = self._batch_select_actions_eager(batch_obs)
+        return actions
+
+    def _batch_explore(self, batch_obs):
+        """The exploring branch of ``batch_act``: the explorer's action for every observation."""
+        stock = type(self)._batch_select_actions is ReplayActorCritic._batch_select_actions
+        if stock:
+            from pfrl_amd.agents import _actor_device_step
+
+            # ... with the explorer's noise (drawn on the host first: it does not depend on the
+            # actions) added and clipped in the same launch
+            actions = _actor_device_step.deterministic_act(self, batch_obs, explore=True)
+            if actions is not None:
+                return list(actions)
+        greedy = (self._batch_select_actions_eager if stock else self._batch_select_actions)(batch_obs)
+        return [self.explorer.select_action(self.t, lambda i=i: greedy[i])
+                for i in range(len(greedy))]
 
     def batch_select_onpolicy_action(self, batch_obs):
         """The policy's own action for every observation, without exploration noise, as a list
@@ -156,9 +181,7 @@ class ReplayActorCritic(AttributeSavingMixin, BatchAgent):
         if self.burnin_action_func is not None and not self._burnin_over():
             actions = [self.burnin_action_func() for _ in range(len(batch_obs))]
         else:
-            greedy = self._batch_select_actions(batch_obs)
-            actions = [self.explorer.select_action(self.t, lambda i=i: greedy[i])
-                       for i in range(len(greedy))]
+            actions = self._batch_explore(batch_obs)
         self.batch_last_obs = list(batch_obs)
         self.batch_last_action = list(actions)
         return actions

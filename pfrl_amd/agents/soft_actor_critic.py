@@ -380,6 +380,13 @@ class SoftActorCritic(ReplayActorCritic):
 
     # -- acting (no explorer: the stochastic policy explores) -----------------------------------
     def batch_select_greedy_action(self, batch_obs, deterministic=False):
+        # one staging transfer + one captured graph with the fused head launch where the policy is
+        # recognised (agents/_actor_device_step.py); None: the policy is called as it is
+        from pfrl_amd.agents import _actor_device_step
+
+        actions = _actor_device_step.squashed_act(self, batch_obs, deterministic)
+        if actions is not None:
+            return actions
         with torch.no_grad(), evaluating(self.policy):
             batch_xs = self.batch_states(batch_obs, self.device, self.phi)
             policy_out = self.policy(batch_xs)

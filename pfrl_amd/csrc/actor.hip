@@ -15,6 +15,7 @@
 // operation in the order of the PyTorch code it replaces (built with -ffp-contract=off).
 #include "common.h"
 #include "row_reduce.h"
+#include "squashed_row.h"
 
 namespace {
 
@@ -82,19 +83,8 @@ __global__ __launch_bounds__(kThreads) void k_squashed_gaussian_bwd(
 // (mean | log_scale) side by side; scale = sqrt(exp(2 clamp(log_scale, lo, hi))) (MODE 0, the
 // arithmetic of train_soft_actor_critic.py:128-141, one rounded f32 operation per torch op) or
 // exp(clamp(log_scale, lo, hi)) (MODE 1).  Replaces chunk / clamp / mul / exp / sqrt forward and
-// their ten backward launches (sqrt, exp, mul, two compares, and, where, fill x2, cat).
-template <int MODE>
-__device__ __forceinline__ float head_scale(float ls, float lo, float hi, float &v) {
-    float c = ls < lo ? lo : ls;          // torch.clamp: min(max(x, lo), hi), NaN passes through
-    c = c > hi ? hi : c;
-    if (MODE == 0) {
-        v = expf(c * 2.f);
-        return sqrtf(v);
-    }
-    v = expf(c);
-    return v;
-}
-
+// their ten backward launches (sqrt, exp, mul, two compares, and, where, fill x2, cat).  Scale,
+// pre-squash sample and tanh: squashed_row.h, shared with the acting launch (actor_act.hip).
 template <int MODE>
 __global__ __launch_bounds__(kThreads) void k_squashed_head_fwd(
     const float *__restrict__ x, int64_t ldx, float lo, float hi, const float *__restrict__ eps,
@@ -103,12 +93,11 @@ __global__ __launch_bounds__(kThreads) void k_squashed_head_fwd(
     if (row >= B) return;
     float s_ladj = 0.f, s_nlp = 0.f;
     for (int a = lane; a < A; a += 64) {
-        float v;
+        float s, u;
         const float l = x[(int64_t)row * ldx + a];
-        const float s = head_scale<MODE>(x[(int64_t)row * ldx + A + a], lo, hi, v);
         const float e = eps[(int64_t)row * A + a];
-        const float u = l + e * s;
-        action[(int64_t)row * A + a] = tanhf(u);
+        action[(int64_t)row * A + a] =
+            squashed_head_action<MODE>(l, x[(int64_t)row * ldx + A + a], lo, hi, true, e, s, u);
         const float d = u - l;
         const float nlp = -(d * d) / (2.f * (s * s)) - logf(s) - 0.9189385332046727f;
         const float z = -2.f * u;

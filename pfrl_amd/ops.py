@@ -128,6 +128,55 @@ def boltzmann_select(q, u, temperature, status, want_probs=False, out=None):
     return out, probs
 
 
+ACTOR_ACT_MAX_A, ACTOR_ACT_MAX_K, ACTOR_ACT_MAX_M = 32, 1024, 4096     # (the gates of csrc/actor_act.hip)
+
+
+def _act_head_args(h, weight, bias, n_out, out, A):
+    M, K = h.shape
+    assert h.dtype == torch.float32 and h.is_contiguous() and weight.dtype == torch.float32
+    assert weight.is_contiguous() and tuple(weight.shape) == (n_out, K) and bias.numel() == n_out
+    if out is None:
+        out = torch.empty((M, A), dtype=torch.float32, device=h.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (M, A) and out.is_contiguous()
+    return M, K, out
+
+
+def squashed_head_act(h, weight, bias, spec, eps=None, want_x=False, out=None):
+    """SAC's acting step behind the policy body in one launch (pfrl_squashed_head_act; reference
+    pfrl/agents/soft_actor_critic.py:317-334): ``h`` [M, K] f32, ``weight`` [2A, K], ``spec`` the
+    ``HeadSpec`` of the recognised head, ``eps`` [M, A] the standard-normal draw or None for the
+    distribution's mode.  Returns (action [M, A], x [M, 2A] or None)."""
+    A = spec.A
+    M, K, out = _act_head_args(h, weight, bias, 2 * A, out, A)
+    assert eps is None or (eps.dtype == torch.float32 and tuple(eps.shape) == (M, A))
+    x = torch.empty((M, 2 * A), dtype=torch.float32, device=h.device) if want_x else None
+    check(_native.lib().pfrl_squashed_head_act(_ptr(h), _ptr(weight), _ptr(bias), spec.lo, spec.hi,
+                                               spec.mode, _ptr(eps), _ptr(x), _ptr(out), M, K, A,
+                                               _stream()), "squashed_head_act")
+    return out, x
+
+
+def deterministic_head_act(h, weight, bias, bound=None, noise=None, low=None, high=None, want_y=False,
+                           want_greedy=False, out=None):
+    """TD3's / DDPG's acting step behind the policy body in one launch (pfrl_deterministic_head_act;
+    reference pfrl/agents/td3.py:262-281): ``h`` [M, K] f32, ``weight`` [A, K], ``bound`` the two
+    vectors [A] of ``BoundByTanh`` or None, ``noise`` [M, A] the explorer's rows with ``low`` /
+    ``high`` [A] (infinite where the explorer has no bound) or None.  Returns (action [M, A], y or
+    None, greedy or None)."""
+    A = weight.shape[0]
+    M, K, out = _act_head_args(h, weight, bias, A, out, A)
+    assert noise is None or (noise.dtype == torch.float32 and tuple(noise.shape) == (M, A)
+                             and low.numel() == A and high.numel() == A)
+    y = torch.empty((M, A), dtype=torch.float32, device=h.device) if want_y else None
+    g = torch.empty((M, A), dtype=torch.float32, device=h.device) if want_greedy else None
+    bs, sh = bound if bound is not None else (None, None)
+    check(_native.lib().pfrl_deterministic_head_act(
+        _ptr(h), _ptr(weight), _ptr(bias), _ptr(bs), _ptr(sh), _ptr(noise),
+        _ptr(low) if noise is not None else None, _ptr(high) if noise is not None else None, _ptr(y),
+        _ptr(g), _ptr(out), M, K, A, _stream()), "deterministic_head_act")
+    return out, y, g
+
+
 def _spatial_hw(fshape):
     """(H, W) if the frame is one 2-D plane ((H, W) or (1, H, W)), else None."""
     dims = [d for d in fshape]
