@@ -1034,6 +1034,37 @@ int pfrl_td3_critic_loss_bwd(const float *const *g_loss, const float *target_q,
                              void *stream);
 int pfrl_neg_mean(const float *q, float *loss, float *unit_g_q, int32_t B, void *stream);
 
+/* NAF: the TD loss of DQN / DoubleDQN with a quadratic Q-function and its gradients with respect to
+ * the four raw head outputs, in one launch.  Replaces
+ *   pfrl/action_value.py                        QuadraticActionValue (greedy_actions, max, evaluate_actions)
+ *   pfrl/q_functions/state_q_functions.py       FCQuadraticStateQFunction.forward behind its Linear layers
+ *   pfrl/agents/dqn.py                          _compute_y_and_t, _compute_target_values, compute_value_loss,
+ *                                               compute_weighted_value_loss
+ *   pfrl/agents/double_dqn.py                   _compute_target_values
+ * All tensors float32, row-major, the raw outputs of the Linear layers before any activation.
+ * Online network at s: v [B], m [B][n] (raw mu), e [B][n] (raw log-diagonal), c [B][n (n - 1) / 2]
+ * (the strictly lower entries in the row-major order (1,0), (2,0), (2,1), ... of
+ * lower_triangular_matrix; NULL when n == 1).  Target network at s': tv, tm, te, tc likewise.
+ * m2 [B][n]: the online network's raw mu at s' (DoubleDQN), else NULL.  action [B][n]; reward,
+ * discount, terminal [B]; weights [B] or NULL.  half_width, centre [n]: scale_by_tanh's constants,
+ * both NULL when mu is not scaled.  low, high [n]: the action box, each may be NULL.
+ *   mu = tanh(m) half_width + centre (or m),  L_ii = exp(e_i),  L_ij = c_k,  d = action - mu,
+ *   w = L^T d,  y = v - |w|^2 / 2                                   (L L^T is never formed)
+ *   a* = min(high, max(low, mu*)),  mu* = the target's mu' or, with m2, the online mu''
+ *   next = v' - |L'^T (a* - mu')|^2 / 2;  with no bounds and no m2: v' itself
+ *   t, the Huber / squared term, weights and mean-or-sum as pfrl_dqn_td_loss
+ * Outputs: out_loss [1], out_y [B], out_abs_delta [B] = |y - t|, and dloss/d(v, m, e, c) as dv [B],
+ * dm [B][n], de [B][n], dc [B][n (n - 1) / 2] (NULL when n == 1).  One workgroup, a fixed order of
+ * every sum, no float atomics: the same inputs give the same bits on every launch.
+ * B >= 1, 1 <= n <= 32; anything else returns PFRL_ERR_ARG and writes nothing. */
+int pfrl_naf_td_loss(const float *v, const float *m, const float *e, const float *c, const float *tv,
+                     const float *tm, const float *te, const float *tc, const float *m2,
+                     const float *action, const float *reward, const float *discount,
+                     const float *terminal, const float *weights, const float *half_width,
+                     const float *centre, const float *low, const float *high, int32_t B, int32_t n,
+                     int clip_delta, int mean, float *out_loss, float *out_y, float *out_abs_delta,
+                     float *dv, float *dm, float *de, float *dc, void *stream);
+
 /* Ragged gather of sampled episodes for recurrent updates: batch_recurrent_experiences
  * (pfrl/replay_buffer.py:219-287) over EpisodicReplayBuffer.sample_episodes (pfrl/replay_buffers/
  * episodic.py:48-85, windows cut by random_subseq).  An episode is a run of consecutive

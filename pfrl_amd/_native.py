@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libpfrl_amd.so")
 # measurement hook (tools/build_variant.sh): another build of the same sources, e.g. other compiler
 # flags, loaded instead of the in-tree library.  Never set by the package, the tests or bench.py.
 _LIB_OVERRIDE = os.environ.get("PFRL_AMD_LIB")
-SOURCES = ["frames.hip", "replay.hip", "sumtree.hip", "rollout.hip", "optim.hip", "tdloss.hip", "operator_td.hip", "bias_act.hip", "noisy.hip", "c51.hip", "iqn.hip", "dueling.hip", "qnet.hip", "actor.hip", "actor_act.hip", "hostplan.hip", "philox.hip", "ppo_gaussian.hip", "trpo.hip", "reinforce.hip", "a2c.hip", "td3.hip"]
+SOURCES = ["frames.hip", "replay.hip", "sumtree.hip", "rollout.hip", "optim.hip", "tdloss.hip", "operator_td.hip", "bias_act.hip", "noisy.hip", "c51.hip", "iqn.hip", "dueling.hip", "qnet.hip", "actor.hip", "actor_act.hip", "hostplan.hip", "philox.hip", "ppo_gaussian.hip", "trpo.hip", "reinforce.hip", "a2c.hip", "td3.hip", "naf.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     # the parity contract is one correctly rounded IEEE op per source op
@@ -255,6 +255,7 @@ EXPORTS = {
     "pfrl_td3_critic_loss": (ctypes.c_int, "ppfpppipppip"),
     "pfrl_td3_critic_loss_bwd": (ctypes.c_int, "ppppiip"),
     "pfrl_neg_mean": (ctypes.c_int, "pppip"),
+    "pfrl_naf_td_loss": (ctypes.c_int, "ppppppppppppppppppiiiipppppppp"),
     "pfrl_philox_normal": (ctypes.c_int, "QQipppppip"),
     "pfrl_profile_enable": (ctypes.c_int, "i"),
     "pfrl_profile_collect": (ctypes.c_int64, "pppq"),

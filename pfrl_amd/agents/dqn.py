@@ -294,7 +294,9 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
         want_errors = has_weight or errors_out is not None
         handed_over = []
         self._flush_backward()
-        if self.use_graphs:
+        # (a capture that fails switches use_graphs off and finishes the update eagerly itself)
+        graphed = self.use_graphs
+        if graphed:
             hand_over = None
             late = None
             if has_weight and errors_out is None and self._replay_stream is not None:
@@ -318,7 +320,7 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
             if self._replay_stream is not None:
                 self.replay_buffer.replay_stream_wait_current()
             self.replay_buffer.update_errors(delta if errors_out is None else errors_out)
-        if not self.use_graphs:
+        if not graphed:
             self.loss_record.extend(loss)
             self.optimizer.zero_grad()
             loss.backward()
@@ -406,6 +408,8 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
         if hasattr(av, "q_dist"):
             self._target_z_values = av.z_values
             return av.q_dist
+        if not self._discrete_values(av):
+            return None         # (nothing to rebuild the action value from: one pass per update)
         return av.q_values
 
     def _action_value(self, model, states, recurrent_state):
@@ -435,8 +439,11 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
                 + exp_batch["discount"] * (1.0 - exp_batch["is_state_terminal"]) * next_q_max)
 
     def _compute_y_and_t(self, exp_batch):
-        batch_size = exp_batch["reward"].shape[0]
         qout = self._action_value(self.model, exp_batch["state"], exp_batch.get("recurrent_state"))
+        return self._y_and_t_of(qout, exp_batch)
+
+    def _y_and_t_of(self, qout, exp_batch):
+        batch_size = exp_batch["reward"].shape[0]
         batch_q = torch.reshape(qout.evaluate_actions(exp_batch["action"]), (batch_size, 1))
         with torch.no_grad():
             batch_q_target = torch.reshape(self._compute_target_values(exp_batch), (batch_size, 1))
@@ -447,15 +454,18 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
     # (categorical agents) set it to None and keep their own.
 
     def _fused_td_loss_applicable(self):
-        """The fused launch computes the stock DQN target (``_fused_td_double`` False) or the
-        stock Double-DQN target (True).  ``_compute_target_values`` / ``_compute_y_and_t`` /
-        ``_compute_loss`` are the reference's extension points (its own DoubleDQN overrides
-        the first): a subclass that overrides any of them keeps the composite path, on
-        every device."""
+        """The fused launches (pfrl_dqn_td_loss and pfrl_dqn_head_td_loss for discrete action
+        values, pfrl_naf_td_loss for a stock NAF Q-function: ``_compute_loss`` picks by
+        ``_discrete_values`` / ``_naf_split``) compute the stock DQN target (``_fused_td_double``
+        False) or the stock Double-DQN target (True).  ``_compute_target_values`` /
+        ``_compute_y_and_t`` / ``_compute_loss`` are the reference's extension points (its own
+        DoubleDQN overrides the first): a subclass that overrides any of them keeps the composite
+        path, on every device."""
         cls = type(self)
         if not (self.fused_td_loss and self.device.type == "cuda" and not self.recurrent
                 and cls._fused_td_double is not None
                 and cls._compute_y_and_t is DQN._compute_y_and_t
+                and cls._y_and_t_of is DQN._y_and_t_of
                 and cls._compute_loss is DQN._compute_loss):
             return False
         if cls._fused_td_double:
@@ -463,6 +473,80 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
 
             return cls._compute_target_values is DoubleDQN._compute_target_values
         return cls._compute_target_values is DQN._compute_target_values
+
+    def _discrete_values(self, av=None):
+        """Does the model return a discrete action value (``q_values`` [B, A]: what the fused DQN
+        launch and the step-batched target pass read)?  Decided once per
+        model and cached like ``_head_split``: a NAF Q-function is known by its class, anything else
+        by the first action value the agent sees (``av``); True until then.  A model that returns
+        something else -- a ``QuadraticActionValue``, a ``SingleActionValue`` -- takes the composite
+        ``_compute_y_and_t`` path, one target pass per update."""
+        cached = self.__dict__.get("_discrete_values_cache")
+        if cached is not None and cached[0] is self.model and (cached[1] is not None or av is None):
+            return cached[1] is not False
+        from pfrl_amd.q_functions import FCQuadraticStateQFunction
+
+        known = None
+        if isinstance(self.model, FCQuadraticStateQFunction):
+            known = False
+        elif av is not None:
+            known = hasattr(av, "q_values")
+        self._discrete_values_cache = (self.model, known)
+        return known is not False
+
+    def _naf_split(self):
+        """The ``_naf_split.NAFSplit`` of a stock NAF model whose target network is its copy: the
+        update then ends in ONE launch (pfrl_naf_td_loss).  None otherwise, and with
+        PFRL_NAF_FUSED=0 (the composite path, for A/B runs)."""
+        cached = self.__dict__.get("_naf_split_cache")
+        if cached is not None and cached[0] is self.model and cached[1] is self.target_model:
+            return cached[2]
+        from pfrl_amd.agents import _naf_split
+
+        out = None
+        if os.environ.get("PFRL_NAF_FUSED", "1") != "0":
+            out = _naf_split.naf_q_function(self.model, self.device)
+            other = _naf_split.naf_q_function(self.target_model, self.device)
+            if out is None or other is None or other.n != out.n or any(
+                    (a is None) != (b is None) or (a is not None and not torch.equal(a, b))
+                    for a, b in zip(out[2:], other[2:])):
+                out = None
+        self._naf_split_cache = (self.model, self.target_model, out)
+        return out
+
+    def _compute_loss_fused_naf(self, split, exp_batch, errors_out, want_errors, record):
+        """The network passes of the composite path in its order -- online at s, for DoubleDQN online
+        at s' in evaluation mode, target at s' -- stopping at the four Linear outputs, then ONE
+        launch for everything behind them, the gradients included; autograd carries them on from
+        the four tensors (so the data-parallel hooks see them as on the composite path)."""
+        from pfrl_amd import ops
+
+        v, m, e, c = split.raw(exp_batch["state"])
+        with torch.no_grad():
+            m2 = None
+            if type(self)._fused_td_double:
+                with evaluating(self.model):
+                    m2 = split.raw_mu(exp_batch["next_state"])
+            tv, tm, te, tc = split.raw(exp_batch["next_state"], self.target_model)
+        action = exp_batch["action"]
+        if not (ops.naf_td_loss_supported(v, m, e, c, tv, tm, te, tc, m2, action)
+                and all(exp_batch[k].dtype == torch.float32 and exp_batch[k].is_contiguous()
+                        for k in ("reward", "discount", "is_state_terminal"))):
+            # outside the launch's gate (another dtype or layout): the composite expression
+            y, t = self._compute_y_and_t(exp_batch)
+            return self._loss_of_y_and_t(y, t, exp_batch, errors_out, want_errors, record)
+        loss, y, delta = ops.naf_td_loss(
+            v, m, e, c, tv, tm, te, tc, m2, action, exp_batch["reward"], exp_batch["discount"],
+            exp_batch["is_state_terminal"], exp_batch.get("weights"), split.half_width, split.centre,
+            split.low, split.high, self.clip_delta, self.batch_accumulator == "mean")
+        self._analytic_backward = None          # (GraphedUpdate: autograd from the loss)
+        self._last_y = y
+        if record:
+            self.q_record.extend(y)
+        if errors_out is not None:
+            del errors_out[:]
+            errors_out.extend(delta.cpu().numpy())
+        return loss, delta
 
     # set by the graph path (GraphedUpdate), which runs backward right after the loss and
     # flushes the queue: the head's batch sums then ride on the trunk backward's fold launch
@@ -490,7 +574,7 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
         self._head_split_cache = (m, out)
         return out
 
-    def _compute_loss_fused(self, exp_batch, errors_out, record):
+    def _compute_loss_fused(self, exp_batch, errors_out, record, want_errors=False):
         from pfrl_amd import distributed, ops
 
         # (data parallel: only inside a captured update whose optimizer takes the head's slabs --
@@ -559,6 +643,11 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
             return loss, delta
         if qout is None:
             qout = self.model(exp_batch["state"])
+        if not self._discrete_values(qout):
+            # no q_values to read (the first update of such a model: from the next one on
+            # _fused_td_loss_applicable says no): the composite expression on the pass just made
+            y, t = self._y_and_t_of(qout, exp_batch)
+            return self._loss_of_y_and_t(y, t, exp_batch, errors_out, want_errors, record)
         with torch.no_grad():
             target_q = self._target_next_action_value(exp_batch).q_values
             next_online = None
@@ -652,7 +741,12 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
         """Returns (loss, |y - t| per sample or None).  ``errors_out`` keeps the
         reference's list-filling form for callers that use it directly."""
         if self._fused_td_loss_applicable():
-            return self._compute_loss_fused(exp_batch, errors_out, record)
+            if self._discrete_values():
+                return self._compute_loss_fused(exp_batch, errors_out, record, want_errors)
+            split = self._naf_split()
+            if split is not None:
+                return self._compute_loss_fused_naf(split, exp_batch, errors_out, want_errors,
+                                                    record)
         if self._fused_operator_loss_applicable():
             return self._compute_loss_fused_operator(exp_batch, errors_out, want_errors, record)
         y, t = self._compute_y_and_t(exp_batch)
@@ -762,6 +856,7 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
             self._last_actions_dev = None
         with torch.no_grad(), evaluating(self.model):
             batch_av = self._evaluate_model(batch_obs)
+            self._discrete_values(batch_av)     # (decided by the first action value seen)
             greedy_dev = batch_av.greedy_actions.detach()
         if self.training and self._explorer_draws_before_greedy():
             # epsilon-greedy family: the per-env draws (rand(), then random_action_func when it
@@ -989,13 +1084,16 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
                                               self.gamma) if U else None
         else:
             big = rbuf.fetch_many(plan_seqs, self.phi, self.gamma) if plan_seqs else None
-        if big is not None and self.batch_target_pass and self._target_is_deterministic():
+        if (big is not None and self.batch_target_pass and self._discrete_values()
+                and self._target_is_deterministic()):
             # no target sync may fall inside this range (the targets would go stale)
             tui = self.target_update_interval
             if (t0 + (hi - lo)) // tui == t0 // tui:
                 ns = big["next_state"]
                 U, B = ns.shape[0], ns.shape[1]
                 raw = self._precompute_target_raw(ns.view((U * B,) + tuple(ns.shape[2:])))
+                if raw is None:
+                    return plan_env, big, t0
                 # captured updates are keyed by buffer addresses: park the values in a
                 # persistent buffer instead of whatever block the allocator handed out
                 key = (U, B, getattr(rbuf.store, "many_parity", 0)) + tuple(raw.shape[1:])

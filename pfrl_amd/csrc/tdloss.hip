@@ -7,15 +7,12 @@
 // launch.  At minibatch 32 those kernels were 27 % of the update's device time
 // (each ~4-5 us of pure launch latency for 32 scalars of work).
 #include "common.h"
+#include "row_reduce.h"
+#include "td_row.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-
-__device__ __forceinline__ float wave_sum_f(float v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 __global__ __launch_bounds__(kThreads) void k_dqn_td_loss(
     const float *__restrict__ q, const int64_t *__restrict__ action,
@@ -43,19 +40,12 @@ __global__ __launch_bounds__(kThreads) void k_dqn_td_loss(
         const float next = qt[best];
         const int act = (int)action[b];
         const float y = q[b * A + act];
-        // t = r + (disc * (1 - term)) * next   -- same association as the reference
-        const float coef = __fmul_rn(discount[b], __fsub_rn(1.0f, terminal[b]));
-        const float t = __fadd_rn(reward[b], __fmul_rn(coef, next));
+        // (same association as the reference: td_row.h)
+        const float t = td_target(reward[b], discount[b], terminal[b], next);
         const float d = __fsub_rn(y, t);
         const float ad = fabsf(d);
         float l, g;
-        if (clip_delta) {
-            l = ad < 1.0f ? __fmul_rn(__fmul_rn(0.5f, ad), ad) : __fsub_rn(ad, 0.5f);
-            g = ad < 1.0f ? d : (d > 0.0f ? 1.0f : -1.0f);
-        } else {
-            l = __fmul_rn(0.5f, __fmul_rn(d, d));
-            g = d;
-        }
+        td_loss_term(d, ad, clip_delta, l, g);
         const float w = weights ? weights[b] : 1.0f;
         local += l * w;
         const float gq = g * w * scale;
@@ -63,7 +53,7 @@ __global__ __launch_bounds__(kThreads) void k_dqn_td_loss(
         out_y[b] = y;
         out_abs_delta[b] = ad;
     }
-    local = wave_sum_f(local);
+    local = wave_sum_f32(local);
     if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = local;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -178,7 +168,7 @@ __device__ __forceinline__ void head_td_row(
         float p = 0.f;
 #pragma unroll
         for (int j = 0; j < KJ; ++j) p = fmaf(hv[j], wv[a][j], p);
-        p = wave_sum_f(p) + bv[a];
+        p = wave_sum_f32(p) + bv[a];
         y = (a == act) ? p : y;
     }
     int best = 0;
@@ -193,18 +183,11 @@ __device__ __forceinline__ void head_td_row(
     float next = tqv[0];
 #pragma unroll
     for (int a = 1; a < A; ++a) next = (a == best) ? tqv[a] : next;
-    const float coef = __fmul_rn(disc, __fsub_rn(1.0f, term));
-    const float t = __fadd_rn(rew, __fmul_rn(coef, next));
+    const float t = td_target(rew, disc, term, next);
     const float d = __fsub_rn(y, t);
     const float ad = fabsf(d);
     float l, g;
-    if (clip_delta) {
-        l = ad < 1.0f ? __fmul_rn(__fmul_rn(0.5f, ad), ad) : __fsub_rn(ad, 0.5f);
-        g = ad < 1.0f ? d : (d > 0.0f ? 1.0f : -1.0f);
-    } else {
-        l = __fmul_rn(0.5f, __fmul_rn(d, d));
-        g = d;
-    }
+    td_loss_term(d, ad, clip_delta, l, g);
     const float gq = g * wt * scale;
     float wsel[KJ];
 #pragma unroll

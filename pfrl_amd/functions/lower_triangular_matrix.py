@@ -20,7 +20,9 @@ def lower_triangular_matrix(diag, non_diag):
     assert isinstance(diag, torch.Tensor) and isinstance(non_diag, torch.Tensor)
     batch, n = diag.shape
     on, below = _flat_positions(n, diag.device)
-    flat = torch.zeros((batch, n * n), dtype=torch.float32, device=diag.device)
+    # (the reference writes float32 zeros; its models are float32.  The diagonal's dtype here, so
+    # that a float64 copy of a model -- the tests' reference -- works instead of raising)
+    flat = torch.zeros((batch, n * n), dtype=diag.dtype, device=diag.device)
     flat[:, below] = non_diag
     flat[:, on] = diag
     return flat.view(batch, n, n)

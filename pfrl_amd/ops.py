@@ -1221,6 +1221,139 @@ def dqn_operator_td_loss(q, target_cur, target_next, next_online, action, reward
                                     discount, terminal, weights, op, param, clip_delta, mean)
 
 
+NAF_MAX_N = 32             # (kMaxN of csrc/naf.hip)
+
+
+class _NAFTDLoss(torch.autograd.Function):
+    """The TD loss of DQN / DoubleDQN with a quadratic (NAF) Q-function over the raw outputs of its
+    four Linear layers; one HIP launch (pfrl_naf_td_loss) computes the loss, Q(s, a), |TD error| and
+    the gradients with respect to the four online tensors."""
+
+    @staticmethod
+    def forward(ctx, v, m, e, c, tv, tm, te, tc, m2, action, reward, discount, terminal, weights,
+                half_width, centre, low, high, clip_delta, mean):
+        B, n = m.shape
+        dev = m.device
+
+        def raw(t):
+            return None if t is None else _ptr(t.detach().contiguous())
+
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        y = torch.empty(B, dtype=torch.float32, device=dev)
+        delta = torch.empty(B, dtype=torch.float32, device=dev)
+        dv = torch.empty(v.shape, dtype=torch.float32, device=dev)
+        dm = torch.empty((B, n), dtype=torch.float32, device=dev)
+        de = torch.empty((B, n), dtype=torch.float32, device=dev)
+        dc = torch.empty((B, n * (n - 1) // 2), dtype=torch.float32, device=dev) if n > 1 else None
+        check(_native.lib().pfrl_naf_td_loss(
+            raw(v), raw(m), raw(e), raw(c) if n > 1 else None, raw(tv), raw(tm), raw(te),
+            raw(tc) if n > 1 else None, raw(m2), raw(action), raw(reward), raw(discount),
+            raw(terminal), raw(weights), raw(half_width), raw(centre), raw(low), raw(high), B, n,
+            int(clip_delta), int(mean), _ptr(loss), _ptr(y), _ptr(delta), _ptr(dv), _ptr(dm),
+            _ptr(de), _ptr(dc), _stream()), "naf_td_loss")
+        ctx.save_for_backward(dv, dm, de, *(() if dc is None else (dc,)))
+        ctx.mark_non_differentiable(y, delta)
+        ctx.set_materialize_grads(False)   # no zero-fill kernels for the unused outputs
+        return loss.view(()), y, delta
+
+    @staticmethod
+    def backward(ctx, g_loss, g_y, g_delta):
+        grads = tuple(g * g_loss for g in ctx.saved_tensors)
+        return grads + (None,) * (20 - len(grads))
+
+
+def naf_td_loss_supported(v, m, e, c, tv, tm, te, tc, m2=None, action=None):
+    """float32 contiguous tensors on one GPU in the shapes of ``naf_td_loss`` with 1 <= n <= 32 and
+    B >= 1: inside the C gate."""
+    if not (torch.is_tensor(m) and m.ndim == 2):
+        return False
+    B, n = m.shape
+    if not (B >= 1 and 1 <= n <= NAF_MAX_N):
+        return False
+    nc = n * (n - 1) // 2
+    wide = [m, e, tm, te] + [t for t in (m2, action) if t is not None]
+    if not all(torch.is_tensor(t) and tuple(t.shape) == (B, n) for t in wide):
+        return False
+    if not all(torch.is_tensor(t) and t.numel() == B for t in (v, tv)):
+        return False
+    tri = [c, tc] if n > 1 else []
+    if not all(torch.is_tensor(t) and tuple(t.shape) == (B, nc) for t in tri):
+        return False
+    return all(t.is_cuda and t.device == m.device and t.dtype == torch.float32 and t.is_contiguous()
+               for t in wide + [v, tv] + tri)
+
+
+def naf_td_loss(v, m, e, c, tv, tm, te, tc, m2, action, reward, discount, terminal, weights,
+                half_width, centre, low, high, clip_delta, mean):
+    """-> (loss scalar with grad, y [B], |y - t| [B]).  Online network at s: ``v`` [B] or [B, 1],
+    ``m`` [B, n] (raw mu), ``e`` [B, n] (raw log-diagonal), ``c`` [B, n (n - 1) / 2] (strictly lower
+    entries in ``lower_triangular_matrix``'s order; None when n == 1); target network at s': ``tv``,
+    ``tm``, ``te``, ``tc``; ``m2``: the online raw mu at s' (DoubleDQN) or None.  ``half_width`` /
+    ``centre`` [n]: ``scale_by_tanh``'s constants, both None when mu is not scaled; ``low`` /
+    ``high`` [n] or None: the action box.  The gradient reaches ``v``, ``m``, ``e`` and ``c``."""
+    return _NAFTDLoss.apply(v, m, e, c, tv, tm, te, tc, m2, action, reward, discount, terminal,
+                            weights, half_width, centre, low, high, clip_delta, mean)
+
+
+def _naf_factor(m, e, c, half_width, centre):
+    """(tanh(m), mu, L) of one network's raw outputs."""
+    B, n = m.shape
+    th = torch.tanh(m)
+    mu = th * half_width + centre if half_width is not None else m
+    L = m.new_zeros((B, n, n))
+    idx = torch.arange(n, device=m.device)
+    L[:, idx, idx] = torch.exp(e)
+    if n > 1:
+        rows, cols = torch.tril_indices(n, n, -1, device=m.device)
+        L[:, rows, cols] = c
+    return th, mu, L
+
+
+def naf_td_loss_closed_form(v, m, e, c, tv, tm, te, tc, m2, action, reward, discount, terminal,
+                            weights, half_width, centre, low, high, clip_delta, mean):
+    """What pfrl_naf_td_loss computes, restated with torch tensor operations in the tensors' own
+    dtype and device (float64 on the CPU in the tests).  No autograd.  Returns (loss, y, |y - t|,
+    (dv, dm, de, dc)); dc is None when n == 1."""
+    B, n = m.shape
+    th, mu, L = _naf_factor(m, e, c, half_width, centre)
+    d = action - mu
+    w = torch.einsum("bij,bi->bj", L, d)
+    y = v.reshape(B) - 0.5 * (w * w).sum(1)
+    nxt = tv.reshape(B)
+    if m2 is not None or low is not None or high is not None:
+        _, tmu, tL = _naf_factor(tm, te, tc, half_width, centre)
+        star = tmu if m2 is None else _naf_factor(m2, te, tc, half_width, centre)[1]
+        if low is not None:
+            star = torch.max(low.expand_as(star), star)
+        if high is not None:
+            star = torch.min(high.expand_as(star), star)
+        twv = torch.einsum("bij,bi->bj", tL, star - tmu)
+        nxt = nxt - 0.5 * (twv * twv).sum(1)
+    t = reward + discount * (1.0 - terminal) * nxt
+    delta = y - t
+    ad = delta.abs()
+    if clip_delta:
+        terms = torch.where(ad < 1, 0.5 * ad * ad, ad - 0.5)
+        g = torch.where(ad < 1, delta, torch.sign(delta))
+    else:
+        terms = 0.5 * delta * delta
+        g = delta
+    wt = weights if weights is not None else torch.ones_like(terms)
+    scale = 1.0 / B if mean else 1.0
+    loss = (terms * wt).sum() * scale
+    gq = g * wt * scale
+    dL = -gq[:, None, None] * d[:, :, None] * w[:, None, :]
+    idx = torch.arange(n, device=m.device)
+    de = dL[:, idx, idx] * L[:, idx, idx]
+    dc = None
+    if n > 1:
+        rows, cols = torch.tril_indices(n, n, -1, device=m.device)
+        dc = dL[:, rows, cols]
+    dmu = gq[:, None] * torch.einsum("bij,bj->bi", L, w)
+    dm = dmu * half_width * (1.0 - th * th) if half_width is not None else dmu
+    return loss, y, ad, (gq.reshape(v.shape), dm, de, dc)
+
+
 class _DQNHeadTDLoss(torch.autograd.Function):
     """The narrow head ``q = h W^T + b``, the TD loss of ``_DQNTDLoss`` and the head's backward
     in one launch (pfrl_dqn_head_td_loss, a wave per row).  The sums over the batch (dL/dW,
