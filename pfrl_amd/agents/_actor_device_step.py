@@ -34,8 +34,9 @@ import numpy as np
 import torch
 
 from pfrl_amd import ops
-from pfrl_amd.agents import _policy_split
-from pfrl_amd.staging import StagingRing
+from pfrl_amd.agents import _capture, _policy_split
+from pfrl_amd.agents._policy_split import hidden_ok
+from pfrl_amd.staging import StagingRing, _align16
 from pfrl_amd.utils.contexts import evaluating
 
 GREEDY, GAUSSIAN, OU = "greedy", "gaussian", "ou"       # explorer kinds of the deterministic step
@@ -53,10 +54,6 @@ def head_enabled():
 
 def graph_enabled():
     return os.environ.get("PFRL_ACTOR_ACT_GRAPH", "1") != "0"
-
-
-def _align16(x):
-    return (x + 15) & ~15
 
 
 # -------------------------------------------------------------------------------------------------
@@ -253,34 +250,25 @@ class ActorStep:
         """Warm-up of ``launch(obs, noise, out)`` on zeros with the device generator put back behind
         it, then -- unless switched off -- the capture.  False: the policy body does not yield what
         the head launch reads."""
-        from pfrl_amd.agents.graphed_update import _capturing
-
         global captures
         dev = self.device
         inp = torch.zeros(_align16(need), dtype=torch.uint8, device=dev)
         out = torch.empty((N, A), dtype=torch.float32, device=dev)
         obs, noise = self._views(inp, N, shape, A, rows)
-        rng = torch.cuda.get_rng_state(dev)
-        cur = torch.cuda.current_stream(dev)
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(cur)
-        ok = True
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                if launch(obs, noise, out) is None:
-                    ok = False
-                    break
-        cur.wait_stream(side)
-        torch.cuda.set_rng_state(rng, dev)          # the warm-up draws are not part of the run
-        if not ok:
-            return False
+
+        def body(i=None):
+            if launch(obs, noise, out) is None:
+                return _capture.REFUSED
+
+        snap = _capture.Snapshot((), (), dev)       # (the generator: warm-up draws are not part of the run)
+        try:
+            if not _capture.warm_up(dev, body):
+                return False
+        finally:
+            snap.restore()
         if not graph_enabled():
             return _Entry(None, None, None)
-        g = torch.cuda.CUDAGraph()
-        with ops.profile_paused(), _capturing(g, self.pool):
-            launch(obs, noise, out)
-        if self.pool is None:
-            self.pool = g.pool()
+        g, _ = _capture.capture(self, body)
         captures += 1
         return _Entry(g, inp, out)
 
@@ -333,11 +321,6 @@ def _step_of(agent):
     return st
 
 
-def _hidden_ok(h, N, lin):
-    return (torch.is_tensor(h) and h.dim() == 2 and h.dtype == torch.float32 and h.is_contiguous()
-            and tuple(h.shape) == (N, lin.in_features))
-
-
 def _applicable(agent, batch_obs):
     """The observations' shape when device, switch, ``phi`` and observations allow the step."""
     if agent.device.type != "cuda" or not head_enabled():
@@ -368,7 +351,7 @@ def squashed_act(agent, batch_obs, deterministic):
     def launch(obs, noise, out):
         with torch.no_grad(), evaluating(policy):
             h = body(obs)
-            if not _hidden_ok(h, N, lin):
+            if not hidden_ok(h, lin, N):
                 return None
             # the draw Normal.sample makes (torch.normal's normal_ on [N, A]): same generator offsets
             eps = None if deterministic else _eps((N, A), torch.float32, h.device)
@@ -409,7 +392,7 @@ def deterministic_act(agent, batch_obs, explore):
     def launch(obs, noise, out):
         with torch.no_grad(), evaluating(policy):
             h = body(obs)
-            if not _hidden_ok(h, N, lin):
+            if not hidden_ok(h, lin, N):
                 return None
             if noise is None:
                 return ops.deterministic_head_act(h, lin.weight, lin.bias, bound, out=out)[0]

@@ -43,9 +43,10 @@ import numpy as np
 import torch
 
 from pfrl_amd import _native, host_plan, ops
-from pfrl_amd.agents._policy_split import prefix_view
+from pfrl_amd.agents import _capture
+from pfrl_amd.agents._policy_split import hidden_ok, prefix_view
 from pfrl_amd.device_store import DeviceActions, DeviceObsBatch
-from pfrl_amd.staging import StagingRing
+from pfrl_amd.staging import StagingRing, _align16
 from pfrl_amd.utils.contexts import evaluating
 
 RUN_AHEAD = 3       # batched steps the host may be ahead of the GPU
@@ -81,10 +82,6 @@ class LastBatch:
 
     def all_set(self, lo, hi):
         return self.cleared is None or not self.cleared[lo:hi].any()
-
-
-def _align16(x):
-    return (x + 15) & ~15
 
 
 def act_split(agent):
@@ -227,8 +224,6 @@ class ActGraph:
         return _act_launches(agent, batch_obs, choice, out)
 
     def _capture(self, agent, batch_obs, N, k, off_choice, need, kind):
-        from pfrl_amd.agents.graphed_update import _capturing
-
         dev = agent.device
         pair = []
         for _ in range(2):
@@ -240,21 +235,18 @@ class ActGraph:
             else:
                 inp[off_choice:off_choice + 4 * N].view(torch.int32).fill_(-1)
             out = torch.empty(N, dtype=torch.int64, device=dev)
-            cur = torch.cuda.current_stream(dev)
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    if self._body(agent, batch_obs, inp, N, k, off_choice, out, kind) is None:
-                        cur.wait_stream(side)
-                        return None
-            cur.wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with ops.profile_paused(), _capturing(g, self.pool):
-                self._body(agent, batch_obs, inp, N, k, off_choice, out, kind)
-            if self.pool is None:
-                self.pool = g.pool()
-            pair.append((g, inp, out))
+
+            def body(i=None, inp=inp, out=out):
+                if self._body(agent, batch_obs, inp, N, k, off_choice, out, kind) is None:
+                    return _capture.REFUSED
+
+            snap = _capture.Snapshot((), (), dev)       # (the generator: warm-up draws are not part of the run)
+            try:
+                if not _capture.warm_up(dev, body):
+                    return None
+            finally:
+                snap.restore()
+            pair.append((_capture.capture(self, body)[0], inp, out))
         return [pair, 0]
 
     def run(self, agent, batch_obs, ring, tok, N, k, off_choice, need, kind=EPS_GREEDY):
@@ -293,8 +285,7 @@ def _act_launches(agent, batch_obs, choice, out=None):
         body, lin = split
         agent._route_observation_layout(batch_obs)
         h = body(agent.batch_states(batch_obs, agent.device, agent.phi))
-        if not (torch.is_tensor(h) and h.dim() == 2 and h.dtype == torch.float32 and h.is_contiguous()
-                and h.shape[1] == lin.in_features):
+        if not hidden_ok(h, lin):
             if out is not None:
                 return None
             greedy = list(agent.model._modules.values())[-1](lin(h)).greedy_actions.detach()
@@ -321,8 +312,7 @@ def _act_launches_boltzmann(agent, batch_obs, u, temperature, out=None):
             body, lin = split
             agent._route_observation_layout(batch_obs)
             h = body(agent.batch_states(batch_obs, agent.device, agent.phi))
-            if (torch.is_tensor(h) and h.dim() == 2 and h.dtype == torch.float32 and h.is_contiguous()
-                    and h.shape[1] == lin.in_features):
+            if hidden_ok(h, lin):
                 return ops.dqn_act_head_boltzmann(h, lin.weight, lin.bias, u, temperature, status,
                                                   out=out)[0]
             if out is not None:

@@ -33,6 +33,13 @@ def prefix_view(seq, drop=1, replacement=None):
     return _view(seq, items[:keep] + tail)
 
 
+def hidden_ok(h, lin, N=None):
+    """``h`` is what a fused head launch reads in front of ``lin``: [N, in_features] float32,
+    contiguous (``N`` None: any number of rows)."""
+    return (torch.is_tensor(h) and h.dim() == 2 and h.dtype == torch.float32 and h.is_contiguous()
+            and h.shape[1] == lin.in_features and (N is None or h.shape[0] == N))
+
+
 def _all_f32(model):
     return all(p.dtype == torch.float32 for p in model.parameters())
 

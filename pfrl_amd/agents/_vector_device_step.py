@@ -33,11 +33,7 @@ import numpy as np
 import torch
 
 from pfrl_amd import _native, host_plan
-from pfrl_amd.staging import StagingRing, on_stream
-
-
-def _align16(x):
-    return (x + 15) & ~15
+from pfrl_amd.staging import StagingRing, _align16, on_stream
 
 
 def enabled():

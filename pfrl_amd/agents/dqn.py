@@ -32,6 +32,7 @@ import torch
 import torch.nn.functional as F
 
 from pfrl_amd import agent
+from pfrl_amd.agents import _capture
 from pfrl_amd.replay_buffer import (AbstractEpisodicReplayBuffer, DeviceExperienceBatch,
                                     ReplayUpdater, batch_experiences,
                                     batch_recurrent_experiences)
@@ -239,7 +240,7 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
         want_overlap = (self.use_graphs and isinstance(replay_buffer, PrioritizedReplayBuffer)
                         and getattr(replay_buffer, "is_device", False))
         if want_overlap if replay_overlap is None else (replay_overlap and want_overlap):
-            self._replay_stream = torch.cuda.Stream(self.device)
+            self._replay_stream = _capture.new_stream(self.device)
             self._fwd_event = torch.cuda.Event()
             self._replay_stream.wait_stream(torch.cuda.current_stream(self.device))
             replay_buffer.set_replay_stream(self._replay_stream)

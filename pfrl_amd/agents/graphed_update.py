@@ -14,56 +14,13 @@ snapshot that is restored afterwards, so no extra optimizer step leaks into
 training.
 """
 import collections
-import gc
 import logging
 import os
 
 import torch
 
 from pfrl_amd import distributed
-
-
-def _capture_kwargs(pool):
-    """Arguments of ``torch.cuda.graph``: the shared memory pool, and thread-local capture error
-    mode -- in the default global mode a HIP call from ANY other thread while this one captures
-    (a process group's watchdog polling events, a runtime helper thread) aborts the process."""
-    kw = {} if pool is None else {"pool": pool}
-    kw["capture_error_mode"] = "thread_local"
-    return kw
-
-
-class _capturing:
-    """``with _capturing(g, pool):`` -- ``torch.cuda.graph`` with the collector paused.  A
-    collection that starts mid-capture runs finalizers on the capturing thread (graphs, pinned
-    buffers and events of an agent that went out of scope): their HIP calls are not allowed in a
-    capture, the error is thrown inside a destructor and the process aborts -- seen as a rare
-    "Fatal Python error: Aborted ... Garbage-collecting" when several agents are built in one
-    process.  ``torch.cuda.graph`` collects once on entry, before the capture begins."""
-
-    def __init__(self, g, pool):
-        self.ctx = torch.cuda.graph(g, **_capture_kwargs(pool))
-
-    def __enter__(self):
-        self.was_enabled = gc.isenabled()
-        r = self.ctx.__enter__()
-        gc.disable()
-        return r
-
-    def __exit__(self, *exc):
-        try:
-            return self.ctx.__exit__(*exc)
-        finally:
-            if self.was_enabled:
-                gc.enable()
-
-
-def _optimizer_tensors(optimizer):
-    out = []
-    for st in optimizer.state.values():
-        for k, v in st.items():
-            if isinstance(v, torch.Tensor):
-                out.append((st, k, v))
-    return out
+from pfrl_amd.agents import _capture
 
 
 def _make_capturable(optimizer, device):
@@ -348,58 +305,40 @@ class GraphedUpdate:
         self._reduce("finish")
         self._step()
 
+    def _ensure_capturable(self):
+        ag = self.agent
+        if not self._capturable_done:
+            if not _make_capturable(ag.optimizer, ag.device):
+                raise RuntimeError("optimizer %s has no capturable mode" % type(ag.optimizer))
+            self._capturable_done = True
+
     def _snapshot(self):
         ag = self.agent
-        params = [p.detach().clone() for p in ag.model.parameters()]
-        bufs = [b.detach().clone() for b in ag.model.buffers()]
-        had_state = len(ag.optimizer.state) > 0
-        opt = [(st, k, v.detach().clone()) for st, k, v in _optimizer_tensors(ag.optimizer)]
-        rng = torch.cuda.get_rng_state(ag.device)
-        return params, bufs, had_state, opt, rng
-
-    def _restore(self, snap):
-        ag = self.agent
-        params, bufs, had_state, opt, rng = snap
-        with torch.no_grad():
-            for p, s in zip(ag.model.parameters(), params):
-                p.copy_(s)
-            for b, s in zip(ag.model.buffers(), bufs):
-                b.copy_(s)
-            if had_state:
-                for st, k, v in opt:
-                    st[k].copy_(v)
-            else:
-                # state was created by the warm-up: reset it to its initial value
-                for st, k, v in _optimizer_tensors(ag.optimizer):
-                    v.zero_()
-        torch.cuda.set_rng_state(rng, ag.device)
+        return _capture.Snapshot([ag.model], [ag.optimizer], ag.device)
 
     # -- the NoisyNet draws of an update as ONE launch in front of its graph ---------------------
     def _noise_feed_ok(self):
-        """The update's networks hold factorised-noise layers on the GPU and csrc/philox.hip
-        reproduces this PyTorch build's torch.randn bit for bit (probed): the draws then leave the
-        captured graph -- one eager launch per replay writes all of them, in the layers' call
-        order, from the device generator (PFRL_NOISE_FEED=0: torch.randn calls inside the graph)."""
-        if os.environ.get("PFRL_NOISE_FEED", "1") == "0" or self.agent.device.type != "cuda":
-            return False
-        from pfrl_amd import ops
+        """The update's networks hold factorised-noise layers and the draws can leave the captured
+        graph (``_capture.noise_feed_available``), in the layers' call order."""
         from pfrl_amd.nn.noisy_linear import FactorizedNoisyLinear
 
-        if not any(isinstance(m, FactorizedNoisyLinear) for m in self.agent.model.modules()):
-            return False
-        return ops.philox_variant(self.agent.device) is not None
+        return (any(isinstance(m, FactorizedNoisyLinear) for m in self.agent.model.modules())
+                and _capture.noise_feed_available(self.agent.device))
 
-    def _noise_buffers(self, sizes, repeat=1):
-        sizes = list(sizes) * repeat
-        offs, pos = [], 0
-        for n in sizes:
-            offs.append(pos)
-            pos += (n + 3) & ~3
-        from pfrl_amd import ops
+    def _warm_up(self, exp_batch, want_errors, repeat=1):
+        """The warm-up of a capture on ``exp_batch`` (``_capture.warm_up_noise``): the noise dict
+        of the entry, or None."""
+        ag = self.agent
 
-        buf = torch.zeros(pos, dtype=torch.float32, device=self.agent.device)
-        plan = ops.RandnPlan(sizes, self.agent.device, out=buf)      # (argument arrays built once)
-        return {"sizes": sizes, "buf": buf, "views": plan.views, "plan": plan}
+        def update(i):
+            ag.optimizer.zero_grad(set_to_none=True)
+            self._forward_backward(exp_batch, want_errors)
+            self._reduce_and_step()
+
+        noise = _capture.warm_up_noise(ag.device, update, self._noise_feed_ok(), repeat)
+        _make_capturable(ag.optimizer, ag.device)   # state created by the warm-up
+        ag.optimizer.zero_grad(set_to_none=True)
+        return noise
 
     def _fill_noise(self, entry):
         noise = entry.get("noise")
@@ -441,51 +380,19 @@ class GraphedUpdate:
         return self._capture_plan(exp_batch, want_errors, collective_in_graph=False)
 
     def _capture_plan(self, exp_batch, want_errors, collective_in_graph):
-        ag = self.agent
-        dev = ag.device
-        if not self._capturable_done:
-            if not _make_capturable(ag.optimizer, dev):
-                raise RuntimeError("optimizer %s has no capturable mode" % type(ag.optimizer))
-            self._capturable_done = True
+        self._ensure_capturable()
         snap = self._snapshot()
         try:
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
-        except AttributeError:
-            pass
-        cur = torch.cuda.current_stream(dev)
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(cur)
-        from pfrl_amd.nn.noisy_linear import NoiseFeed, noise_feed
-
-        noise = None
-        rec = NoiseFeed() if self._noise_feed_ok() else None
-        try:
-            with torch.cuda.stream(side):
-                for it in range(2):
-                    if it == 1 and rec is not None and rec.sizes:
-                        # the first warm-up drew through torch.randn and noted the sizes: from here
-                        # on the layers read views of one static buffer (filled once for the rest of
-                        # the warm-up; the RNG state is restored below either way)
-                        noise = self._noise_buffers(rec.sizes)
-                        self._fill_noise({"noise": noise})
-                    feed = rec if it == 0 else (NoiseFeed(noise["views"]) if noise else None)
-                    with noise_feed(feed):
-                        ag.optimizer.zero_grad(set_to_none=True)
-                        self._forward_backward(exp_batch, want_errors)
-                        self._reduce_and_step()
-            cur.wait_stream(side)
-            _make_capturable(ag.optimizer, dev)  # state created by the warm-up
-            ag.optimizer.zero_grad(set_to_none=True)
+            noise = self._warm_up(exp_batch, want_errors)
             distributed._CAPTURE_COLLECTIVES[0] = bool(collective_in_graph)
             try:
-                with noise_feed(NoiseFeed(noise["views"]) if noise else None):
+                with _capture.serving(noise):
                     entry = self._capture_graphs(exp_batch, want_errors, collective_in_graph)
                 entry["noise"] = noise
             finally:
                 distributed._CAPTURE_COLLECTIVES[0] = False
         finally:
-            cur.wait_stream(side)
-            self._restore(snap)
+            snap.restore()
         return entry
 
     def _capture_graphs(self, exp_batch, want_errors, collective_in_graph):
@@ -493,12 +400,7 @@ class GraphedUpdate:
         entry = {}
 
         def graph_of(fn):
-            g = torch.cuda.CUDAGraph()
-            with _capturing(g, self.pool):
-                r = fn()
-            if self.pool is None:
-                self.pool = g.pool()
-            return g, r
+            return _capture.capture(self, fn)
 
         # plan: graphs interleaved with the two things that cannot be captured --
         # the caller's hand-over after the forward pass ("after_forward", pipeline
@@ -579,7 +481,7 @@ class GraphedUpdate:
                 runs.append(rec.results())
         finally:
             ag.optimizer.zero_grad(set_to_none=True)
-            self._restore(snap)
+            snap.restore()
         runs = [r for r in runs[1:] if [n for n, _ in r] == [n for n, _ in runs[-1]]]
         out = []
         for i, (name, _) in enumerate(runs[-1]):
@@ -613,12 +515,7 @@ class GraphedUpdate:
 
     def _capture_range(self, big):
         ag = self.agent
-        dev = ag.device
         U = next(iter(big.values())).shape[0]
-        if not self._capturable_done:
-            if not _make_capturable(ag.optimizer, dev):
-                raise RuntimeError("optimizer %s has no capturable mode" % type(ag.optimizer))
-            self._capturable_done = True
 
         def body():
             losses, ys = [], []
@@ -630,50 +527,19 @@ class GraphedUpdate:
                 ys.append(ag._last_y.reshape(-1))
             return torch.stack(losses), torch.cat(ys)
 
+        self._ensure_capturable()
         snap = self._snapshot()
         try:
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
-        except AttributeError:
-            pass
-        cur = torch.cuda.current_stream(dev)
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(cur)
-        from pfrl_amd.nn.noisy_linear import NoiseFeed, noise_feed
-
-        noise = None
-        rec = NoiseFeed() if self._noise_feed_ok() else None
-        try:
-            with torch.cuda.stream(side):
-                # warm-up on the first update of the range only (same kernels for all U)
-                for it in range(2):
-                    if it == 1 and rec is not None and rec.sizes:
-                        noise = self._noise_buffers(rec.sizes, repeat=U)    # (every update draws anew)
-                        self._fill_noise({"noise": noise})
-                    feed = rec if it == 0 else (NoiseFeed(noise["views"]) if noise else None)
-                    with noise_feed(feed):
-                        ag.optimizer.zero_grad(set_to_none=True)
-                        self._forward_backward({k: v[0] for k, v in big.items()}, False)
-                        self._reduce_and_step()
-            cur.wait_stream(side)
-            _make_capturable(ag.optimizer, dev)
-            ag.optimizer.zero_grad(set_to_none=True)
-            g = torch.cuda.CUDAGraph()
+            # warm-up on the first update of the range only (same kernels for all U); every update
+            # draws anew: the captured range must consume exactly the draws recorded x U
+            noise = self._warm_up({k: v[0] for k, v in big.items()}, False, repeat=U)
             distributed._CAPTURE_COLLECTIVES[0] = self.split_for_allreduce
-            cap_feed = NoiseFeed(noise["views"]) if noise else None
             try:
-                with _capturing(g, self.pool), noise_feed(cap_feed):
-                    losses, ys = body()
+                g, (losses, ys) = _capture.capture(self, body, _capture.serving(noise))
             finally:
                 distributed._CAPTURE_COLLECTIVES[0] = False
-            # (the captured range must have consumed exactly the draws recorded x U)
-            assert cap_feed is None or cap_feed.at == len(noise["views"]), \
-                "the captured updates drew %d normals' tensors, %d were recorded" % (
-                    cap_feed.at, len(noise["views"]))
-            if self.pool is None:
-                self.pool = g.pool()
         finally:
-            cur.wait_stream(side)
-            self._restore(snap)
+            snap.restore()
         return {"graph": g, "losses": losses, "ys": ys, "noise": noise}
 
     def _replay_items(self, items, bucket):
@@ -777,14 +643,9 @@ class CapturedStep:
         return tuple(sorted((k, v.data_ptr(), tuple(v.shape)) for k, v in batch.items()
                             if isinstance(v, torch.Tensor)))
 
-    def _tensors(self):
-        out = []
-        for m in self.modules:
-            out.extend(p for p in m.parameters())
-            out.extend(b for b in m.buffers())
-        return out
-
     def _capture(self, batch, variant=None, step=None, warm=None, repeat=1, prewarm=None):
+        from pfrl_amd.nn.noisy_linear import noise_feed
+
         dev = self.device
         if step is None:
             step = (lambda: self.fn(batch)) if variant is None else (lambda: self.fn(batch, variant))
@@ -793,85 +654,34 @@ class CapturedStep:
         for opt in self.optimizers:
             if not _make_capturable(opt, dev):
                 raise RuntimeError("optimizer %s has no capturable mode" % type(opt))
-        saved = [t.detach().clone() for t in self._tensors()]
-        had_state = [len(o.state) > 0 for o in self.optimizers]
-        opt_saved = [[(st, k, v.detach().clone()) for st, k, v in _optimizer_tensors(o)]
-                     for o in self.optimizers]
-        rng = torch.cuda.get_rng_state(dev)
-        try:
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
-        except AttributeError:
-            pass
+        snap = _capture.Snapshot(self.modules, self.optimizers, dev)
 
-        def restore():
-            # undo the warm-up steps (also when the capture itself fails)
-            with torch.no_grad():
-                for t, s in zip(self._tensors(), saved):
-                    t.copy_(s)
-                for o, had, sv in zip(self.optimizers, had_state, opt_saved):
-                    if had:
-                        for st, k, v in sv:
-                            st[k].copy_(v)
-                    else:
-                        for st, k, v in _optimizer_tensors(o):
-                            v.zero_()
-            torch.cuda.set_rng_state(rng, dev)
+        def warm_pass(i):
+            if i == 0 and prewarm is not None:
+                with noise_feed(None):      # (not part of the step: its draws are not recorded)
+                    prewarm()
+            warm()
 
-        from pfrl_amd.nn.noisy_linear import NoiseFeed, noise_feed
-
-        cur = torch.cuda.current_stream(dev)
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(cur)
-        noise = None
-        rec = NoiseFeed() if self._noise_feed_ok() else None
         if self.device_lr is not None:
             self.device_lr.sync()
             self.device_lr.install()
         try:
-            with torch.cuda.stream(side), _no_distribution_validation():
-                if prewarm is not None:
-                    prewarm()
-                # first warm-up: the step draws its normals as usual and their sizes are noted;
-                # from then on they are views of one buffer that ONE launch fills per replay
-                with noise_feed(rec):
-                    warm()
-                if rec is not None and rec.sizes:
-                    noise = self._noise_buffers(rec.sizes, repeat)
-                    noise["plan"].run()
-                with noise_feed(NoiseFeed(noise["views"]) if noise else None):
-                    warm()
-            cur.wait_stream(side)
+            with _no_distribution_validation():
+                # (any step may draw normals -- Normal.rsample -- so the feed needs no noisy layer)
+                noise = _capture.warm_up_noise(dev, warm_pass, self._noise_feed_ok(), repeat)
             for opt in self.optimizers:
                 _make_capturable(opt, dev)  # state created by the warm-up
                 opt.zero_grad(set_to_none=True)
-            g = torch.cuda.CUDAGraph()
-            with _capturing(g, self.pool), _no_distribution_validation(), \
-                    noise_feed(NoiseFeed(noise["views"]) if noise else None):
-                out = step()
-            if self.pool is None:
-                self.pool = g.pool()
+            g, out = _capture.capture(self, step, _no_distribution_validation(),
+                                      _capture.serving(noise))
         finally:
-            cur.wait_stream(side)
-            restore()
+            snap.restore()
             if self.device_lr is not None:
                 self.device_lr.restore()
         return g, out, noise
 
     def _noise_feed_ok(self):
-        if os.environ.get("PFRL_NOISE_FEED", "1") == "0" or torch.device(self.device).type != "cuda":
-            return False
-        from pfrl_amd import ops
-
-        return ops.philox_variant(self.device) is not None
-
-    def _noise_buffers(self, sizes, repeat):
-        from pfrl_amd import ops
-
-        sizes = list(sizes) * repeat
-        pos = sum((n + 3) & ~3 for n in sizes)
-        buf = torch.zeros(pos, dtype=torch.float32, device=self.device)
-        plan = ops.RandnPlan(sizes, self.device, out=buf)
-        return {"sizes": sizes, "buf": buf, "views": plan.views, "plan": plan}
+        return _capture.noise_feed_available(self.device)
 
     def run_range(self, big, variants):
         """``big``: dict of tensors with a leading update axis U (one fused gather for all

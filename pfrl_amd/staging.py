@@ -9,6 +9,11 @@ import numpy as np
 import torch
 
 
+def _align16(x):
+    """Offsets and lengths inside a slot are multiples of 16 bytes."""
+    return (x + 15) & ~15
+
+
 class StagingRing:
     # seconds the host spent waiting for a slot's previous transfer (all rings): how far ahead of
     # the device the host runs shows up here, not in its own work
@@ -72,7 +77,7 @@ class StagingRing:
     def commit(self, token, nbytes):
         """Ship the first ``nbytes`` of a reserved slot in ONE async transfer; returns the
         device uint8 buffer of that slot (valid until the ring wraps)."""
-        self._ship(token, (int(nbytes) + 15) & ~15)
+        self._ship(token, _align16(int(nbytes)))
         return self._dev[token]
 
     def commit_to(self, token, nbytes, dst):
@@ -81,7 +86,7 @@ class StagingRing:
         dev_ptr = self._dev_ptr[token]
         self._dev_ptr[token] = dst.data_ptr()
         try:
-            self._ship(token, (int(nbytes) + 15) & ~15)
+            self._ship(token, _align16(int(nbytes)))
         finally:
             self._dev_ptr[token] = dev_ptr
         return dst
@@ -97,7 +102,7 @@ class StagingRing:
         off = 0
         for a in arrays:
             a = np.ascontiguousarray(a)
-            off = (off + 15) & ~15
+            off = _align16(off)
             nb = a.nbytes
             if off + nb > self.slot_bytes or off + nb > dst.numel():
                 raise ValueError("staging slot / destination too small: need %d bytes" % (off + nb))
@@ -124,13 +129,13 @@ class StagingRing:
         for a in arrays:
             a = np.ascontiguousarray(a)
             nb = a.nbytes
-            off = (off + 15) & ~15
+            off = _align16(off)
             if off + nb > self.slot_bytes:
                 raise ValueError("staging slot too small: need %d bytes" % (off + nb))
             hb[off:off + nb] = a.view(np.uint8).reshape(-1)
             key.append((off, a.dtype.num, a.shape))
             off += nb
-        self._ship(i, (off + 15) & ~15)
+        self._ship(i, _align16(off))
         key = tuple(key)
         outs = self._views[i].get(key)
         if outs is None:
