@@ -4,6 +4,8 @@ examples/atari/train_drqn_ale.py with `pfrl` replaced by `pfrl_amd`: a CNN + LST
 a ``RecurrentSequential``, an ``EpisodicReplayBuffer`` and ``DoubleDQN(recurrent=True)`` that
 replays sub-episodes of ``--episodic-update-len`` steps.  Episodes live on the host and the
 update runs eagerly (packed sequences of varying shape), so this also runs with ``--gpu -1``.
+On a GPU the LSTM's acting step is one fused launch (``pfrl_lstm_cell_fwd``, csrc/lstm.hip;
+``PFRL_LSTM_CELL=0`` keeps ``nn.LSTM``); the sequence update and its backward stay in the library.
 
     python examples/train_drqn_batch_synthetic.py --gpu -1 --steps 2000 --num-envs 8 \\
         --p-done 0.05 --replay-start-size 300 --batch-size 4

@@ -1065,6 +1065,20 @@ int pfrl_naf_td_loss(const float *v, const float *m, const float *e, const float
                      int clip_delta, int mean, float *out_loss, float *out_y, float *out_abs_delta,
                      float *dv, float *dm, float *de, float *dc, void *stream);
 
+/* One LSTM time step in one launch (csrc/lstm.hip; torch.nn.LSTM, one layer, gate order i, f, g, o):
+ *   gates = x w_ih^T + h0 w_hh^T + b_ih + b_hh
+ *   c1 = sigmoid(f) c0 + sigmoid(i) tanh(g),   h1 = sigmoid(o) tanh(c1)
+ * x [N][I], h0 / c0 [N][H], w_ih [4H][I], w_hh [4H][H], b_ih / b_hh [4H], h1 / c1 [N][H], all f32
+ * row-major contiguous.  h0 NULL: zeros, and the w_hh part of the reduction is skipped; c0 NULL:
+ * zeros; b_ih / b_hh NULL: absent.  y [N][H] or NULL: a second copy of h1 (the step's output, which
+ * torch.nn.LSTM returns in a tensor of its own next to the state).  Every sum has one fixed order, no atomics: the same inputs give
+ * the same bits on every launch.  Envelope: 1 <= N <= 256 (64 rows per workgroup, further rows in
+ * a second grid dimension that reads the weights again), I >= 1, H >= 1, 4 H max(I, H) < 2^31;
+ * outside it, or with a NULL x / w_ih / w_hh / h1 / c1, PFRL_ERR_ARG and nothing is written. */
+int pfrl_lstm_cell_fwd(const float *x, const float *h0, const float *c0, const float *w_ih,
+                       const float *w_hh, const float *b_ih, const float *b_hh, float *h1, float *c1,
+                       float *y, int32_t N, int32_t I, int32_t H, void *stream);
+
 /* Ragged gather of sampled episodes for recurrent updates: batch_recurrent_experiences
  * (pfrl/replay_buffer.py:219-287) over EpisodicReplayBuffer.sample_episodes (pfrl/replay_buffers/
  * episodic.py:48-85, windows cut by random_subseq).  An episode is a run of consecutive

@@ -1716,6 +1716,36 @@ def dueling_softmax(ya, ys, n_actions, n_atoms):
     return _DuelingSoftmax.apply(ya, ys, n_actions, n_atoms)
 
 
+LSTM_CELL_MAX_N = 256          # (the gate of csrc/lstm.hip: four 64-row workgroups per block of units)
+
+
+def lstm_cell_supported(N, I, H):
+    """Shapes inside the envelope of :func:`lstm_cell_step` (pfrl_lstm_cell_fwd refuses the others)."""
+    return 1 <= N <= LSTM_CELL_MAX_N and I >= 1 and H >= 1 and 4 * H * max(I, H) < 2 ** 31
+
+
+def lstm_cell_step(x, h0, c0, w_ih, w_hh, b_ih, b_hh, want_output=False):
+    """One ``torch.nn.LSTM`` time step in one launch (pfrl_lstm_cell_fwd, csrc/lstm.hip): ``x``
+    [N, I], ``h0`` / ``c0`` [N, H] or None (zeros: start of sequence), ``w_ih`` [4H, I], ``w_hh``
+    [4H, H], ``b_ih`` / ``b_hh`` [4H] or None, all f32 and contiguous.  Returns (h1, c1), both
+    [N, H]; with ``want_output`` (h1, c1, y), y a second buffer holding h1, as ``nn.LSTM`` returns
+    its output and its state in separate tensors.  No host synchronisation: the launch goes to the current stream."""
+    N, I = x.shape
+    H = w_hh.shape[1]
+    tensors = [t for t in (x, h0, c0, w_ih, w_hh, b_ih, b_hh) if t is not None]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device for t in tensors)
+    assert tuple(w_ih.shape) == (4 * H, I) and tuple(w_hh.shape) == (4 * H, H)
+    assert all(s is None or tuple(s.shape) == (N, H) for s in (h0, c0))
+    assert all(b is None or b.numel() == 4 * H for b in (b_ih, b_hh))
+    h1 = torch.empty((N, H), dtype=torch.float32, device=x.device)
+    c1 = torch.empty((N, H), dtype=torch.float32, device=x.device)
+    y = torch.empty((N, H), dtype=torch.float32, device=x.device) if want_output else None
+    check(_native.lib().pfrl_lstm_cell_fwd(_ptr(x), _ptr(h0), _ptr(c0), _ptr(w_ih), _ptr(w_hh), _ptr(b_ih),
+                                           _ptr(b_hh), _ptr(h1), _ptr(c1), _ptr(y), N, I, H, _stream()),
+          "lstm_cell_step")
+    return (h1, c1, y) if want_output else (h1, c1)
+
+
 # ---------------------------------------------------------------------------------------------
 # torch.randn on the device generator as ONE launch for several draws (csrc/philox.hip)
 # ---------------------------------------------------------------------------------------------
