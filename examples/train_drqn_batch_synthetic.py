@@ -5,7 +5,9 @@ a ``RecurrentSequential``, an ``EpisodicReplayBuffer`` and ``DoubleDQN(recurrent
 replays sub-episodes of ``--episodic-update-len`` steps.  Episodes live on the host and the
 update runs eagerly (packed sequences of varying shape), so this also runs with ``--gpu -1``.
 On a GPU the LSTM's acting step is one fused launch (``pfrl_lstm_cell_fwd``, csrc/lstm.hip;
-``PFRL_LSTM_CELL=0`` keeps ``nn.LSTM``); the sequence update and its backward stay in the library.
+``PFRL_LSTM_CELL=0`` keeps ``nn.LSTM``), and the update's three sequence passes and the backward run
+the LSTM's recurrence as one launch per time step (``pfrl_lstm_seq_fwd`` / ``pfrl_lstm_seq_bwd``,
+csrc/lstm_seq.hip; ``PFRL_LSTM_SEQ=0`` keeps ``nn.LSTM``).
 
     python examples/train_drqn_batch_synthetic.py --gpu -1 --steps 2000 --num-envs 8 \\
         --p-done 0.05 --replay-start-size 300 --batch-size 4

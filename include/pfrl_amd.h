@@ -1079,6 +1079,30 @@ int pfrl_lstm_cell_fwd(const float *x, const float *h0, const float *c0, const f
                        const float *w_hh, const float *b_ih, const float *b_hh, float *h1, float *c1,
                        float *y, int32_t N, int32_t I, int32_t H, void *stream);
 
+/* The recurrence of a packed LSTM sequence, one launch per time step (csrc/lstm_seq.hip; same
+ * semantics as above).  Rows are time-major as a PackedSequence lays them out: batch_sizes[0 .. T)
+ * is a HOST array, non-increasing, each >= 1, batch_sizes[0] <= 256; step t owns rows off_t =
+ * sum_{s<t} batch_sizes[s] onwards, R = off_T rows in all.
+ *   p [R][4H]: x w_ih^T + b_ih + b_hh, computed by the caller;  w_hh [4H][H]
+ *   h0 / c0 [n_0][H] or NULL (zeros; h0 NULL: step 0 has no reduction)
+ *   y / c [R][H]: h_t and c_t of every row;  hn / cn [n_0][H]: the last h / c of every sequence
+ *   gates [R][4H] or NULL: the four ACTIVATED gates, which pfrl_lstm_seq_bwd reads
+ * Fixed summation order, no atomics: the same bits on every call.  T >= 1, H >= 1, R 4H < 2^31 and
+ * non-NULL p / w_hh / y / c / hn / cn / batch_sizes, else PFRL_ERR_ARG and nothing is launched. */
+int pfrl_lstm_seq_fwd(const float *p, const float *h0, const float *c0, const float *w_hh, float *y,
+                      float *c, float *gates, float *hn, float *cn, const int32_t *batch_sizes,
+                      int32_t T, int32_t H, void *stream);
+
+/* ... and its gradient, T + 1 launches (T where dh0 is NULL).  dy [R][H], dhn / dcn [n_0][H] or NULL
+ * (zeros): gradients of y, hn, cn;  gates, c, c0, w_hh, batch_sizes as given to / written by the
+ * forward call.  Writes da [R][4H] (the gradient of p), dh0 [n_0][H] (NULL: not wanted) and
+ * dc0 [n_0][H], which is required: it carries dc from step to step and ends as c0's gradient.
+ * Same envelope and refusals as pfrl_lstm_seq_fwd; dy, w_hh, gates, c, da, dc0 must be non-NULL and
+ * da must start on 16 bytes. */
+int pfrl_lstm_seq_bwd(const float *dy, const float *dhn, const float *dcn, const float *w_hh,
+                      const float *gates, const float *c, const float *c0, float *da, float *dh0,
+                      float *dc0, const int32_t *batch_sizes, int32_t T, int32_t H, void *stream);
+
 /* Ragged gather of sampled episodes for recurrent updates: batch_recurrent_experiences
  * (pfrl/replay_buffer.py:219-287) over EpisodicReplayBuffer.sample_episodes (pfrl/replay_buffers/
  * episodic.py:48-85, windows cut by random_subseq).  An episode is a run of consecutive

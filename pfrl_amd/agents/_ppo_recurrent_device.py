@@ -30,6 +30,7 @@ from torch.nn.utils.rnn import PackedSequence
 from pfrl_amd import ops
 from pfrl_amd.agents.ppo_host import (_limit_sequence_length,
                                       _yield_subset_of_sequences_with_fixed_number_of_items)
+from pfrl_amd.nn.recurrent import first_order_sequences
 from pfrl_amd.utils.clip_l2_grad_norm import clip_grad_norm_device_
 from pfrl_amd.utils.contexts import evaluating
 from pfrl_amd.utils.recurrent import (_map_state, mask_recurrent_state_at, one_step_forward,
@@ -161,7 +162,8 @@ class RecurrentDeviceRollouts:
         (flat_dev, t_dev, e_dev) = [x.clone() for x in a._stage.upload([flat, first // N, first % N])]
         x = a._features(refs_col[flat_dev])
         rs = cols.pick(t_dev, e_dev)
-        y, _ = a.model(PackedSequence(x, torch.from_numpy(batch_sizes)), rs)
+        with first_order_sequences():
+            y, _ = a.model(PackedSequence(x, torch.from_numpy(batch_sizes)), rs)
         return unwrap_packed_sequences_recursive(y), flat_dev
 
     def update(self):

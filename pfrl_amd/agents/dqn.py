@@ -33,6 +33,7 @@ import torch.nn.functional as F
 
 from pfrl_amd import agent
 from pfrl_amd.agents import _capture
+from pfrl_amd.nn.recurrent import first_order_sequences
 from pfrl_amd.replay_buffer import (AbstractEpisodicReplayBuffer, DeviceExperienceBatch,
                                     ReplayUpdater, batch_experiences,
                                     batch_recurrent_experiences)
@@ -417,7 +418,8 @@ class DQN(agent.AttributeSavingMixin, agent.BatchAgent):
         """``model(states)``; for a recurrent model ``states`` is a list of per-episode batches
         and the result is flat in packed (time-major) order (reference :391-399, :415-420)."""
         if self.recurrent:
-            return pack_and_forward(model, states, recurrent_state)[0]
+            with first_order_sequences():      # (an LSTM member's sequence: csrc/lstm_seq.hip)
+                return pack_and_forward(model, states, recurrent_state)[0]
         return model(states)
 
     def _target_next_action_value(self, exp_batch):

@@ -28,6 +28,7 @@ Out of scope: recurrent TRPO on the device rollout, a fused Fisher-vector produc
 one captured graph.
 """
 import collections
+import contextlib
 import random
 from logging import getLogger
 
@@ -101,6 +102,8 @@ def _clip_l2_grad_norm_host_(parameters, max_norm):
 
 class _HostTRPO(HostRollouts):
     """The list-of-dicts rollout of ``ppo_host`` with TRPO's update (reference :318-334)."""
+
+    sequence_route = staticmethod(contextlib.nullcontext)     # (the Fisher-vector product differentiates twice)
 
     def _normaliser_learns(self, transitions):
         a = self.agent

@@ -4,7 +4,9 @@ recurrent_branched.py:6-26).
 The calling convention is ``torch.nn.LSTM``'s with packed input:
 ``module(packed_sequences, recurrent_state) -> (packed_output, new_recurrent_state)``, where a
 ``None`` state means "start of sequence"."""
+import contextlib
 import os
+import threading
 
 import torch
 from torch import nn
@@ -29,7 +31,7 @@ def lstm_cell_step_or_none(member, packed, state):
     Returns what ``nn.LSTM`` returns for a one-step packed input: the ``PackedSequence`` over h1 and
     the state ``(h1[None], c1[None])`` of shape (1, N, H), output and state in separate buffers (an
     in-place member behind the LSTM must not reach the carried state).  Training passes (gradients enabled) and
-    whole sequences keep the library path."""
+    whole sequences are :func:`lstm_sequence_or_none`'s, or the library's."""
     if os.environ.get("PFRL_LSTM_CELL", "1") == "0" or torch.is_grad_enabled():
         return None
     if (type(member) is not nn.LSTM or member.num_layers != 1 or member.bidirectional
@@ -50,6 +52,48 @@ def lstm_cell_step_or_none(member, packed, state):
     h1, c1, y = ops.lstm_cell_step(x.contiguous(), h0, c0, w_ih.contiguous(),
                                    member.weight_hh_l0.contiguous(), b_ih, b_hh, want_output=True)
     return PackedSequence(y, packed.batch_sizes, None, None), (h1[None], c1[None])
+
+
+_route = threading.local()
+
+
+@contextlib.contextmanager
+def first_order_sequences():
+    """Inside this block (per thread) a container may take an ``nn.LSTM`` member's whole packed
+    sequence, training passes included, to ``ops.lstm_sequence``.  The caller vouches that it
+    differentiates the result at most once and does not hold it to ``nn.LSTM``'s bits: the DQN family's
+    and PPO's recurrent updates enter it; TRPO (a Fisher-vector product differentiates twice),
+    REINFORCE and bare container calls do not, and keep ``nn.LSTM``."""
+    before, _route.sequences = getattr(_route, "sequences", False), True
+    try:
+        yield
+    finally:
+        _route.sequences = before
+
+
+def lstm_sequence_or_none(member, packed, state):
+    """A packed sequence through an ``nn.LSTM`` member as ``ops.lstm_sequence`` (one library GEMM for
+    the input projection, one launch of csrc/lstm_seq.hip per time step, forward and backward), or
+    None: outside :func:`first_order_sequences`, with ``PFRL_LSTM_SEQ=0``, or where the member, the
+    input or the shape is not the kernels'.  Returns what ``nn.LSTM`` returns."""
+    if not getattr(_route, "sequences", False) or os.environ.get("PFRL_LSTM_SEQ", "1") == "0":
+        return None
+    if (type(member) is not nn.LSTM or member.num_layers != 1 or member.bidirectional
+            or member.proj_size != 0):
+        return None
+    if not isinstance(packed, PackedSequence) or packed.sorted_indices is not None:
+        return None
+    x, w_ih = packed.data, member.weight_ih_l0
+    if not (x.is_cuda and x.dtype == torch.float32 and w_ih.dtype == torch.float32
+            and w_ih.device == x.device and _native.available()):
+        return None
+    sizes = packed.batch_sizes.tolist()          # (a CPU tensor: no synchronisation)
+    if not ops.lstm_sequence_supported(sizes, x.shape[1], member.hidden_size):
+        return None
+    h0, c0 = (None, None) if state is None else (state[0][0], state[1][0])
+    b_ih, b_hh = (member.bias_ih_l0, member.bias_hh_l0) if member.bias else (None, None)
+    y, hn, cn = ops.lstm_sequence(x, sizes, h0, c0, w_ih, member.weight_hh_l0, b_ih, b_hh)
+    return PackedSequence(y, packed.batch_sizes, None, None), (hn[None], cn[None])
 
 
 class RecurrentSequential(Recurrent, nn.Sequential):
@@ -75,6 +119,7 @@ class RecurrentSequential(Recurrent, nn.Sequential):
                 if not packed:
                     h, packed = wrap_packed_sequences_recursive(h, *packing), True
                 h, s = (lstm_cell_step_or_none(member, h, recurrent_state[slot])
+                        or lstm_sequence_or_none(member, h, recurrent_state[slot])
                         or member(h, recurrent_state[slot]))
                 new_state.append(s)
                 slot += 1

@@ -1746,6 +1746,105 @@ def lstm_cell_step(x, h0, c0, w_ih, w_hh, b_ih, b_hh, want_output=False):
     return (h1, c1, y) if want_output else (h1, c1)
 
 
+def lstm_sequence_supported(batch_sizes, I, H):
+    """Packed shapes inside the envelope of :func:`lstm_sequence` (csrc/lstm_seq.hip refuses the
+    others): ``batch_sizes`` a sequence of ints, non-increasing and >= 1, at most 256 rows a step."""
+    b = [int(n) for n in batch_sizes]
+    return (len(b) >= 1 and b[-1] >= 1 and b[0] <= LSTM_CELL_MAX_N and all(m >= n for m, n in zip(b, b[1:]))
+            and I >= 1 and H >= 1 and 4 * H * max(sum(b), I, H) < 2 ** 31)
+
+
+def _sizes_array(batch_sizes):
+    return (ctypes.c_int32 * len(batch_sizes))(*batch_sizes)     # a HOST array: no synchronisation
+
+
+def lstm_seq_forward(p, batch_sizes, h0, c0, w_hh, want_gates):
+    """The forward recurrence over the packed rows of ``p`` [R, 4H] (pfrl_lstm_seq_fwd, one launch per
+    time step): (y [R, H], c [R, H], activated gates [R, 4H] or None, hn [n0, H], cn [n0, H])."""
+    R, H, dev = p.shape[0], w_hh.shape[1], p.device
+    tensors = [t for t in (p, h0, c0, w_hh) if t is not None]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in tensors)
+    assert tuple(p.shape) == (sum(batch_sizes), 4 * H) and tuple(w_hh.shape) == (4 * H, H)
+    assert all(s is None or tuple(s.shape) == (batch_sizes[0], H) for s in (h0, c0))
+    y, c = (torch.empty((R, H), dtype=torch.float32, device=dev) for _ in range(2))
+    hn, cn = (torch.empty((batch_sizes[0], H), dtype=torch.float32, device=dev) for _ in range(2))
+    gates = torch.empty((R, 4 * H), dtype=torch.float32, device=dev) if want_gates else None
+    check(_native.lib().pfrl_lstm_seq_fwd(_ptr(p), _ptr(h0), _ptr(c0), _ptr(w_hh), _ptr(y), _ptr(c), _ptr(gates),
+                                          _ptr(hn), _ptr(cn), _sizes_array(batch_sizes), len(batch_sizes), H,
+                                          _stream()), "lstm_seq_forward")
+    return y, c, gates, hn, cn
+
+
+def lstm_seq_backward(dy, dhn, dcn, w_hh, gates, c, c0, batch_sizes, want_dh0=True):
+    """The reverse recurrence (pfrl_lstm_seq_bwd): (dA [R, 4H], the gradient of ``p``; dh0 or None;
+    dc0), from the gradients of y, hn, cn (``dhn`` / ``dcn`` None: zeros)."""
+    R, H, dev = c.shape[0], w_hh.shape[1], c.device
+    tensors = [t for t in (dy, dhn, dcn, w_hh, gates, c, c0) if t is not None]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in tensors)
+    assert tuple(dy.shape) == (R, H) and tuple(gates.shape) == (R, 4 * H) and R == sum(batch_sizes)
+    assert all(s is None or tuple(s.shape) == (batch_sizes[0], H) for s in (dhn, dcn, c0))
+    da = torch.empty((R, 4 * H), dtype=torch.float32, device=dev)
+    dh0 = torch.empty((batch_sizes[0], H), dtype=torch.float32, device=dev) if want_dh0 else None
+    dc0 = torch.empty((batch_sizes[0], H), dtype=torch.float32, device=dev)
+    check(_native.lib().pfrl_lstm_seq_bwd(_ptr(dy), _ptr(dhn), _ptr(dcn), _ptr(w_hh), _ptr(gates), _ptr(c), _ptr(c0),
+                                          _ptr(da), _ptr(dh0), _ptr(dc0), _sizes_array(batch_sizes),
+                                          len(batch_sizes), H, _stream()), "lstm_seq_backward")
+    return da, dh0, dc0
+
+
+class _LSTMSequence(torch.autograd.Function):
+    """``nn.LSTM`` over a packed sequence: the input projection and the weight gradients are library
+    GEMMs over all rows, the recurrence and its reverse are csrc/lstm_seq.hip.  First order only."""
+
+    @staticmethod
+    def forward(ctx, x, h0, c0, w_ih, w_hh, b_ih, b_hh, batch_sizes):
+        bias = b_ih if b_hh is None else b_hh if b_ih is None else b_ih + b_hh
+        p = x @ w_ih.t() if bias is None else torch.addmm(bias, x, w_ih.t())
+        train = any(ctx.needs_input_grad)
+        y, c, gates, hn, cn = lstm_seq_forward(p, batch_sizes, h0, c0, w_hh, want_gates=train)
+        if train:
+            ctx.save_for_backward(x, h0, c0, w_ih, w_hh, y, c, gates)
+            ctx.batch_sizes, ctx.biases = batch_sizes, (b_ih is not None, b_hh is not None)
+        return y, hn, cn
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy, dhn, dcn):
+        x, h0, c0, w_ih, w_hh, y, c, gates = ctx.saved_tensors
+        b, need = ctx.batch_sizes, ctx.needs_input_grad
+        dy = torch.zeros_like(y) if dy is None else dy.contiguous()
+        dhn, dcn = (None if d is None else d.contiguous() for d in (dhn, dcn))
+        da, dh0, dc0 = lstm_seq_backward(dy, dhn, dcn, w_hh, gates, c, c0, b, want_dh0=need[1])
+        dx = da @ w_ih if need[0] else None
+        dw_ih = da.t() @ x if need[3] else None
+        dw_hh = None
+        if need[4]:     # h_{t-1} of every row: the initial state, then the output rows one step back
+            off = [0]
+            for n in b:
+                off.append(off[-1] + n)
+            first = y.new_zeros((b[0], y.shape[1])) if h0 is None else h0
+            h_prev = torch.cat([first] + [y[off[t - 1]:off[t - 1] + b[t]] for t in range(1, len(b))])
+            dw_hh = da.t() @ h_prev
+        db = da.sum(0) if (need[5] or need[6]) else None
+        return (dx, dh0, dc0 if need[2] else None, dw_ih, dw_hh, db if need[5] else None,
+                db if need[6] else None, None)
+
+
+def lstm_sequence(x, batch_sizes, h0, c0, w_ih, w_hh, b_ih, b_hh):
+    """``torch.nn.LSTM`` (one layer, one direction, f32) over the packed rows ``x`` [R, I] of a
+    time-major ``PackedSequence`` with the given ``batch_sizes`` (ints on the host; a CPU tensor as
+    ``PackedSequence.batch_sizes`` serves): (y [R, H], hn [n0, H], cn [n0, H]).  ``h0`` / ``c0`` [n0, H]
+    or None (zeros), biases [4H] or None.  Differentiable once in x, h0, c0 and the parameters."""
+    b = tuple(int(n) for n in batch_sizes)
+    H = w_hh.shape[1]
+    tensors = [t for t in (x, h0, c0, w_ih, w_hh, b_ih, b_hh) if t is not None]
+    assert all(t.dtype == torch.float32 and t.device == x.device for t in tensors)
+    assert lstm_sequence_supported(b, x.shape[1], H) and x.shape[0] == sum(b)
+    assert tuple(w_ih.shape) == (4 * H, x.shape[1]) and tuple(w_hh.shape) == (4 * H, H)
+    h0, c0 = (None if s is None else s.contiguous() for s in (h0, c0))
+    return _LSTMSequence.apply(x.contiguous(), h0, c0, w_ih, w_hh.contiguous(), b_ih, b_hh, b)
+
+
 # ---------------------------------------------------------------------------------------------
 # torch.randn on the device generator as ONE launch for several draws (csrc/philox.hip)
 # ---------------------------------------------------------------------------------------------
