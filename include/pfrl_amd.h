@@ -1103,6 +1103,42 @@ int pfrl_lstm_seq_bwd(const float *dy, const float *dhn, const float *dcn, const
                       const float *gates, const float *c, const float *c0, float *da, float *dh0,
                       float *dc0, const int32_t *batch_sizes, int32_t T, int32_t H, void *stream);
 
+/* One GRU time step in one launch (csrc/gru.hip; torch.nn.GRU, one layer, gate order r, z, n):
+ *   r = sigmoid(W_ir x + b_ir + W_hr h0 + b_hr),   z likewise
+ *   q = W_hn h0 + b_hn,   n = tanh(W_in x + b_in + r q),   h1 = (1 - z) n + z h0
+ * x [N][I], h0 [N][H], w_ih [3H][I], w_hh [3H][H], b_ih / b_hh [3H], h1 [N][H], all f32 row-major
+ * contiguous.  h0 NULL: zeros, and the w_hh part of the reduction is skipped; b_ih / b_hh NULL:
+ * absent.  y [N][H] or NULL: a second copy of h1 (the step's output, which torch.nn.GRU returns in a
+ * tensor of its own next to the state).  Fixed summation order, no atomics: the same bits on every
+ * launch.  Envelope: 1 <= N <= 256, I >= 1, H >= 1, 3 H max(I, H) < 2^31; outside it, or with a
+ * NULL x / w_ih / w_hh / h1, PFRL_ERR_ARG and nothing is written. */
+int pfrl_gru_cell_fwd(const float *x, const float *h0, const float *w_ih, const float *w_hh,
+                      const float *b_ih, const float *b_hh, float *h1, float *y, int32_t N, int32_t I,
+                      int32_t H, void *stream);
+
+/* The recurrence of a packed GRU sequence, one launch per time step (csrc/gru_seq.hip; rows and
+ * batch_sizes as pfrl_lstm_seq_fwd's: a HOST array, non-increasing, each >= 1, at most 256).
+ *   p [R][3H]: x w_ih^T + b_ih + [b_hr, b_hz, 0], computed by the caller;  w_hh [3H][H]
+ *   b_hn [H] or NULL: the hidden-side bias of the candidate, which the reset gate scales
+ *   h0 [n_0][H] or NULL (zeros: step 0 has no reduction)
+ *   y [R][H]: h_t of every row;  hn [n_0][H]: the last h of every sequence
+ *   saved [R][4H] or NULL: r, z, n and q = h w_hn^T + b_hn, which pfrl_gru_seq_bwd reads
+ * T >= 1, H >= 1, R 4H < 2^31 and non-NULL p / w_hh / y / hn / batch_sizes, else PFRL_ERR_ARG and
+ * nothing is launched. */
+int pfrl_gru_seq_fwd(const float *p, const float *h0, const float *w_hh, const float *b_hn, float *y,
+                     float *saved, float *hn, const int32_t *batch_sizes, int32_t T, int32_t H,
+                     void *stream);
+
+/* ... and its gradient, T + 1 launches (T where dh0 is NULL).  dy [R][H], dhn [n_0][H] or NULL
+ * (zeros): gradients of y and hn;  saved, y, h0, w_hh, batch_sizes as given to / written by the
+ * forward call.  Writes dp [R][3H] = [da_r, da_z, da_n] (the gradient of p), dq [R][3H] =
+ * [da_r, da_z, da_n r] (the gradient of h w_hh^T + b_hh), dh0 [n_0][H] (NULL: not wanted) and uses
+ * carry [n_0][H], which is required: it takes the direct term dh z from step to step.  Same
+ * envelope and refusals as pfrl_gru_seq_fwd; dy, w_hh, saved, y, dp, dq, carry must be non-NULL. */
+int pfrl_gru_seq_bwd(const float *dy, const float *dhn, const float *w_hh, const float *saved,
+                     const float *y, const float *h0, float *dp, float *dq, float *dh0, float *carry,
+                     const int32_t *batch_sizes, int32_t T, int32_t H, void *stream);
+
 /* Ragged gather of sampled episodes for recurrent updates: batch_recurrent_experiences
  * (pfrl/replay_buffer.py:219-287) over EpisodicReplayBuffer.sample_episodes (pfrl/replay_buffers/
  * episodic.py:48-85, windows cut by random_subseq).  An episode is a run of consecutive

@@ -25,6 +25,19 @@ class Recurrent(object):
         raise NotImplementedError
 
 
+def _kernel_member_and_input(member, cls, packed):
+    """What the four routes below ask of the member and its input alike: a plain one-layer,
+    one-direction ``cls`` in f32 on the device of a ``PackedSequence`` without ``sorted_indices``."""
+    if (type(member) is not cls or member.num_layers != 1 or member.bidirectional
+            or member.proj_size != 0):
+        return False
+    if not isinstance(packed, PackedSequence) or packed.sorted_indices is not None:
+        return False
+    x, w_ih = packed.data, member.weight_ih_l0
+    return (x.is_cuda and x.dtype == torch.float32 and w_ih.dtype == torch.float32
+            and w_ih.device == x.device and _native.available())
+
+
 def lstm_cell_step_or_none(member, packed, state):
     """One acting step of an ``nn.LSTM`` member as one launch (``ops.lstm_cell_step``), or None where
     the member, the input or the mode is not the kernel's: the caller then runs the member itself.
@@ -34,16 +47,9 @@ def lstm_cell_step_or_none(member, packed, state):
     whole sequences are :func:`lstm_sequence_or_none`'s, or the library's."""
     if os.environ.get("PFRL_LSTM_CELL", "1") == "0" or torch.is_grad_enabled():
         return None
-    if (type(member) is not nn.LSTM or member.num_layers != 1 or member.bidirectional
-            or member.proj_size != 0):
-        return None
-    if (not isinstance(packed, PackedSequence) or packed.batch_sizes.numel() != 1
-            or packed.sorted_indices is not None):
+    if not _kernel_member_and_input(member, nn.LSTM, packed) or packed.batch_sizes.numel() != 1:
         return None
     x, w_ih = packed.data, member.weight_ih_l0
-    if not (x.is_cuda and x.dtype == torch.float32 and w_ih.dtype == torch.float32
-            and w_ih.device == x.device and _native.available()):
-        return None
     N, H = x.shape[0], member.hidden_size
     if not ops.lstm_cell_supported(N, x.shape[1], H):
         return None
@@ -59,9 +65,9 @@ _route = threading.local()
 
 @contextlib.contextmanager
 def first_order_sequences():
-    """Inside this block (per thread) a container may take an ``nn.LSTM`` member's whole packed
-    sequence, training passes included, to ``ops.lstm_sequence``.  The caller vouches that it
-    differentiates the result at most once and does not hold it to ``nn.LSTM``'s bits: the DQN family's
+    """Inside this block (per thread) a container may take an ``nn.LSTM`` or ``nn.GRU`` member's whole
+    packed sequence, training passes included, to ``ops.lstm_sequence`` / ``ops.gru_sequence``.  The
+    caller vouches that it differentiates the result at most once and does not hold it to ``nn.LSTM``'s bits: the DQN family's
     and PPO's recurrent updates enter it; TRPO (a Fisher-vector product differentiates twice),
     REINFORCE and bare container calls do not, and keep ``nn.LSTM``."""
     before, _route.sequences = getattr(_route, "sequences", False), True
@@ -78,15 +84,9 @@ def lstm_sequence_or_none(member, packed, state):
     input or the shape is not the kernels'.  Returns what ``nn.LSTM`` returns."""
     if not getattr(_route, "sequences", False) or os.environ.get("PFRL_LSTM_SEQ", "1") == "0":
         return None
-    if (type(member) is not nn.LSTM or member.num_layers != 1 or member.bidirectional
-            or member.proj_size != 0):
-        return None
-    if not isinstance(packed, PackedSequence) or packed.sorted_indices is not None:
+    if not _kernel_member_and_input(member, nn.LSTM, packed):
         return None
     x, w_ih = packed.data, member.weight_ih_l0
-    if not (x.is_cuda and x.dtype == torch.float32 and w_ih.dtype == torch.float32
-            and w_ih.device == x.device and _native.available()):
-        return None
     sizes = packed.batch_sizes.tolist()          # (a CPU tensor: no synchronisation)
     if not ops.lstm_sequence_supported(sizes, x.shape[1], member.hidden_size):
         return None
@@ -94,6 +94,41 @@ def lstm_sequence_or_none(member, packed, state):
     b_ih, b_hh = (member.bias_ih_l0, member.bias_hh_l0) if member.bias else (None, None)
     y, hn, cn = ops.lstm_sequence(x, sizes, h0, c0, w_ih, member.weight_hh_l0, b_ih, b_hh)
     return PackedSequence(y, packed.batch_sizes, None, None), (hn[None], cn[None])
+
+
+def gru_cell_step_or_none(member, packed, state):
+    """:func:`lstm_cell_step_or_none` for an ``nn.GRU`` member (``ops.gru_cell_step``, csrc/gru.hip;
+    ``PFRL_GRU_CELL=0`` keeps the library).  The state is ``nn.GRU``'s: one tensor ``h1[None]`` of
+    shape (1, N, H), in a buffer of its own next to the output."""
+    if os.environ.get("PFRL_GRU_CELL", "1") == "0" or torch.is_grad_enabled():
+        return None
+    if not _kernel_member_and_input(member, nn.GRU, packed) or packed.batch_sizes.numel() != 1:
+        return None
+    x = packed.data
+    if not ops.gru_cell_supported(x.shape[0], x.shape[1], member.hidden_size):
+        return None
+    b_ih, b_hh = (member.bias_ih_l0, member.bias_hh_l0) if member.bias else (None, None)
+    h1, y = ops.gru_cell_step(x.contiguous(), None if state is None else state[0].contiguous(),
+                              member.weight_ih_l0.contiguous(), member.weight_hh_l0.contiguous(), b_ih, b_hh,
+                              want_output=True)
+    return PackedSequence(y, packed.batch_sizes, None, None), h1[None]
+
+
+def gru_sequence_or_none(member, packed, state):
+    """:func:`lstm_sequence_or_none` for an ``nn.GRU`` member (``ops.gru_sequence``, csrc/gru_seq.hip;
+    ``PFRL_GRU_SEQ=0`` keeps the library): only inside :func:`first_order_sequences`."""
+    if not getattr(_route, "sequences", False) or os.environ.get("PFRL_GRU_SEQ", "1") == "0":
+        return None
+    if not _kernel_member_and_input(member, nn.GRU, packed):
+        return None
+    x = packed.data
+    sizes = packed.batch_sizes.tolist()          # (a CPU tensor: no synchronisation)
+    if not ops.gru_sequence_supported(sizes, x.shape[1], member.hidden_size):
+        return None
+    b_ih, b_hh = (member.bias_ih_l0, member.bias_hh_l0) if member.bias else (None, None)
+    y, hn = ops.gru_sequence(x, sizes, None if state is None else state[0], member.weight_ih_l0,
+                             member.weight_hh_l0, b_ih, b_hh)
+    return PackedSequence(y, packed.batch_sizes, None, None), hn[None]
 
 
 class RecurrentSequential(Recurrent, nn.Sequential):
@@ -120,6 +155,8 @@ class RecurrentSequential(Recurrent, nn.Sequential):
                     h, packed = wrap_packed_sequences_recursive(h, *packing), True
                 h, s = (lstm_cell_step_or_none(member, h, recurrent_state[slot])
                         or lstm_sequence_or_none(member, h, recurrent_state[slot])
+                        or gru_cell_step_or_none(member, h, recurrent_state[slot])
+                        or gru_sequence_or_none(member, h, recurrent_state[slot])
                         or member(h, recurrent_state[slot]))
                 new_state.append(s)
                 slot += 1

@@ -1845,6 +1845,131 @@ def lstm_sequence(x, batch_sizes, h0, c0, w_ih, w_hh, b_ih, b_hh):
     return _LSTMSequence.apply(x.contiguous(), h0, c0, w_ih, w_hh.contiguous(), b_ih, b_hh, b)
 
 
+def gru_cell_supported(N, I, H):
+    """Shapes inside the envelope of :func:`gru_cell_step` (pfrl_gru_cell_fwd refuses the others)."""
+    return 1 <= N <= LSTM_CELL_MAX_N and I >= 1 and H >= 1 and 3 * H * max(I, H) < 2 ** 31
+
+
+def gru_cell_step(x, h0, w_ih, w_hh, b_ih, b_hh, want_output=False):
+    """One ``torch.nn.GRU`` time step in one launch (pfrl_gru_cell_fwd, csrc/gru.hip): ``x`` [N, I],
+    ``h0`` [N, H] or None (zeros: start of sequence), ``w_ih`` [3H, I], ``w_hh`` [3H, H], ``b_ih`` /
+    ``b_hh`` [3H] or None, all f32 and contiguous.  Returns h1 [N, H]; with ``want_output`` (h1, y),
+    y a second buffer holding h1, as ``nn.GRU`` returns its output and its state in separate
+    tensors.  No host synchronisation: the launch goes to the current stream."""
+    N, I = x.shape
+    H = w_hh.shape[1]
+    tensors = [t for t in (x, h0, w_ih, w_hh, b_ih, b_hh) if t is not None]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device for t in tensors)
+    assert tuple(w_ih.shape) == (3 * H, I) and tuple(w_hh.shape) == (3 * H, H)
+    assert h0 is None or tuple(h0.shape) == (N, H)
+    assert all(b is None or b.numel() == 3 * H for b in (b_ih, b_hh))
+    h1 = torch.empty((N, H), dtype=torch.float32, device=x.device)
+    y = torch.empty((N, H), dtype=torch.float32, device=x.device) if want_output else None
+    check(_native.lib().pfrl_gru_cell_fwd(_ptr(x), _ptr(h0), _ptr(w_ih), _ptr(w_hh), _ptr(b_ih), _ptr(b_hh),
+                                          _ptr(h1), _ptr(y), N, I, H, _stream()), "gru_cell_step")
+    return (h1, y) if want_output else h1
+
+
+def gru_sequence_supported(batch_sizes, I, H):
+    """Packed shapes inside the envelope of :func:`gru_sequence` (csrc/gru_seq.hip refuses the
+    others): ``batch_sizes`` a sequence of ints, non-increasing and >= 1, at most 256 rows a step."""
+    b = [int(n) for n in batch_sizes]
+    return (len(b) >= 1 and b[-1] >= 1 and b[0] <= LSTM_CELL_MAX_N and all(m >= n for m, n in zip(b, b[1:]))
+            and I >= 1 and H >= 1 and 4 * H * max(sum(b), I, H) < 2 ** 31)
+
+
+def gru_seq_forward(p, batch_sizes, h0, w_hh, b_hn, want_saved):
+    """The forward recurrence over the packed rows of ``p`` [R, 3H] (pfrl_gru_seq_fwd, one launch per
+    time step): (y [R, H], saved (r, z, n, q) [R, 4H] or None, hn [n0, H])."""
+    R, H, dev = p.shape[0], w_hh.shape[1], p.device
+    tensors = [t for t in (p, h0, w_hh, b_hn) if t is not None]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in tensors)
+    assert tuple(p.shape) == (sum(batch_sizes), 3 * H) and tuple(w_hh.shape) == (3 * H, H)
+    assert h0 is None or tuple(h0.shape) == (batch_sizes[0], H)
+    assert b_hn is None or b_hn.numel() == H
+    y = torch.empty((R, H), dtype=torch.float32, device=dev)
+    hn = torch.empty((batch_sizes[0], H), dtype=torch.float32, device=dev)
+    saved = torch.empty((R, 4 * H), dtype=torch.float32, device=dev) if want_saved else None
+    check(_native.lib().pfrl_gru_seq_fwd(_ptr(p), _ptr(h0), _ptr(w_hh), _ptr(b_hn), _ptr(y), _ptr(saved), _ptr(hn),
+                                         _sizes_array(batch_sizes), len(batch_sizes), H, _stream()),
+          "gru_seq_forward")
+    return y, saved, hn
+
+
+def gru_seq_backward(dy, dhn, w_hh, saved, y, h0, batch_sizes, want_dh0=True):
+    """The reverse recurrence (pfrl_gru_seq_bwd): (dP [R, 3H], the gradient of ``p``; dQ [R, 3H], the
+    gradient of the hidden-side pre-activations; dh0 or None), from the gradients of y and hn
+    (``dhn`` None: zeros)."""
+    R, H, dev = y.shape[0], w_hh.shape[1], y.device
+    tensors = [t for t in (dy, dhn, w_hh, saved, y, h0) if t is not None]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in tensors)
+    assert tuple(dy.shape) == (R, H) and tuple(saved.shape) == (R, 4 * H) and R == sum(batch_sizes)
+    assert all(s is None or tuple(s.shape) == (batch_sizes[0], H) for s in (dhn, h0))
+    dp, dq = (torch.empty((R, 3 * H), dtype=torch.float32, device=dev) for _ in range(2))
+    dh0, carry = (torch.empty((batch_sizes[0], H), dtype=torch.float32, device=dev) for _ in range(2))
+    check(_native.lib().pfrl_gru_seq_bwd(_ptr(dy), _ptr(dhn), _ptr(w_hh), _ptr(saved), _ptr(y), _ptr(h0), _ptr(dp),
+                                         _ptr(dq), _ptr(dh0 if want_dh0 else None), _ptr(carry),
+                                         _sizes_array(batch_sizes), len(batch_sizes), H, _stream()),
+          "gru_seq_backward")
+    return dp, dq, (dh0 if want_dh0 else None)
+
+
+class _GRUSequence(torch.autograd.Function):
+    """``nn.GRU`` over a packed sequence: the input projection and the weight gradients are library
+    GEMMs over all rows, the recurrence and its reverse are csrc/gru_seq.hip.  First order only."""
+
+    @staticmethod
+    def forward(ctx, x, h0, w_ih, w_hh, b_ih, b_hh, batch_sizes):
+        H = w_hh.shape[1]
+        bias, b_hn = b_ih, None
+        if b_hh is not None:        # b_hr and b_hz fold into the projection; b_hn is scaled by r: the kernel's
+            bias = torch.zeros_like(b_hh) if b_ih is None else b_ih.clone()
+            bias[:2 * H] += b_hh[:2 * H]
+            b_hn = b_hh[2 * H:].contiguous()
+        p = x @ w_ih.t() if bias is None else torch.addmm(bias, x, w_ih.t())
+        train = any(ctx.needs_input_grad)
+        y, saved, hn = gru_seq_forward(p, batch_sizes, h0, w_hh, b_hn, want_saved=train)
+        if train:
+            ctx.save_for_backward(x, h0, w_ih, w_hh, y, saved)
+            ctx.batch_sizes = batch_sizes
+        return y, hn
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy, dhn):
+        x, h0, w_ih, w_hh, y, saved = ctx.saved_tensors
+        b, need = ctx.batch_sizes, ctx.needs_input_grad
+        dy = torch.zeros_like(y) if dy is None else dy.contiguous()
+        dhn = None if dhn is None else dhn.contiguous()
+        dp, dq, dh0 = gru_seq_backward(dy, dhn, w_hh, saved, y, h0, b, want_dh0=need[1])
+        dx = dp @ w_ih if need[0] else None
+        dw_ih = dp.t() @ x if need[2] else None
+        dw_hh = None
+        if need[3]:     # h_{t-1} of every row: the initial state, then the output rows one step back
+            off = [0]
+            for n in b:
+                off.append(off[-1] + n)
+            first = y.new_zeros((b[0], y.shape[1])) if h0 is None else h0
+            h_prev = torch.cat([first] + [y[off[t - 1]:off[t - 1] + b[t]] for t in range(1, len(b))])
+            dw_hh = dq.t() @ h_prev
+        return (dx, dh0, dw_ih, dw_hh, dp.sum(0) if need[4] else None, dq.sum(0) if need[5] else None, None)
+
+
+def gru_sequence(x, batch_sizes, h0, w_ih, w_hh, b_ih, b_hh):
+    """``torch.nn.GRU`` (one layer, one direction, f32) over the packed rows ``x`` [R, I] of a
+    time-major ``PackedSequence`` with the given ``batch_sizes`` (ints on the host; a CPU tensor as
+    ``PackedSequence.batch_sizes`` serves): (y [R, H], hn [n0, H]).  ``h0`` [n0, H] or None (zeros),
+    biases [3H] or None.  Differentiable once in x, h0 and the parameters."""
+    b = tuple(int(n) for n in batch_sizes)
+    H = w_hh.shape[1]
+    tensors = [t for t in (x, h0, w_ih, w_hh, b_ih, b_hh) if t is not None]
+    assert all(t.dtype == torch.float32 and t.device == x.device for t in tensors)
+    assert gru_sequence_supported(b, x.shape[1], H) and x.shape[0] == sum(b)
+    assert tuple(w_ih.shape) == (3 * H, x.shape[1]) and tuple(w_hh.shape) == (3 * H, H)
+    h0 = None if h0 is None else h0.contiguous()
+    return _GRUSequence.apply(x.contiguous(), h0, w_ih, w_hh.contiguous(), b_ih, b_hh, b)
+
+
 # ---------------------------------------------------------------------------------------------
 # torch.randn on the device generator as ONE launch for several draws (csrc/philox.hip)
 # ---------------------------------------------------------------------------------------------
