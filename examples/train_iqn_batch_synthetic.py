@@ -3,8 +3,10 @@
 examples/atari/reproduction/iqn/train_iqn.py (ImplicitQuantileQFunction with the DQN trunk
 as psi, a 64-cosine embedding as phi and Linear(3136, 512) / Linear(512, n_actions) as f;
 N = N' = 64, K = 32; Adam(5e-5, eps 1e-2 / 32); uniform replay; mean accumulator) run through
-the batched driver with `pfrl` replaced by `pfrl_amd`.  On the GPU the loss behind the three
-network passes is one launch (pfrl_iqn_loss)."""
+the batched driver with `pfrl` replaced by `pfrl_amd`.  On the GPU the threshold embedding of
+every network pass (cosines, phi's Linear and ReLU, the product with psi) is one launch
+(pfrl_iqn_embed_fwd, with pfrl_iqn_embed_bwd going back) and the loss behind the three passes is
+another (pfrl_iqn_loss)."""
 import argparse
 import os
 import sys

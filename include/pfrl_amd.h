@@ -1139,6 +1139,30 @@ int pfrl_gru_seq_bwd(const float *dy, const float *dhn, const float *w_hh, const
                      const float *y, const float *h0, float *dp, float *dq, float *dh0, float *carry,
                      const int32_t *batch_sizes, int32_t T, int32_t H, void *stream);
 
+/* IQN's threshold embedding head in one launch (csrc/iqn_embed.hip; pfrl/agents/iqn.py:11-60 and
+ * the product of :104-109), M = B N rows:
+ *   out[r][h] = psi[r / N][h] * relu(b[h] + sum_i cos(taus[r] * i_pi[i]) * w[h][i])
+ * taus [M], i_pi [n] (pi, 2 pi, ... n pi as the caller rounds them), w [H][n], b [H], psi [B][H],
+ * out [M][H], all f32 row-major contiguous.  emb [M][n] or NULL: the cosines, which
+ * pfrl_iqn_embed_bwd reads.  Fixed summation order, no atomics: the same bits on every launch.
+ * Envelope: B >= 1, 1 <= N <= 64, 1 <= n <= 64, H >= 1, M H < 2^31, H n < 2^31; outside it, or with a
+ * NULL operand other than emb, PFRL_ERR_ARG and nothing is written. */
+int pfrl_iqn_embed_fwd(const float *taus, const float *i_pi, const float *w, const float *b,
+                       const float *psi, float *out, float *emb, int32_t B, int32_t N, int32_t n,
+                       int32_t H, void *stream);
+
+/* ... and its gradient for g = dL/d out [M][H], with emb as the forward call wrote it (the ReLU
+ * mask is recomputed from it and has the forward's bits):
+ *   dpsi[bb][h] = sum_n' g[bb N + n'][h] relu(pre),   dpre = g psi [pre > 0],
+ *   dw[h][i] = sum_r dpre[r][h] emb[r][i],   db[h] = sum_r dpre[r][h];   none for taus.
+ * Two launches for M <= 256.  Above, the rows are reduced in slabs of 256 that a third launch
+ * (pfrl_splitk_reduce) folds, slab 0 first: part then is a 16-byte aligned workspace of part_floats >=
+ * ceil(M / 256) * (r4(H n) + r4(H)) floats, r4 rounding up to a multiple of 4, and dw / db are 16-byte
+ * aligned.  Same envelope and refusals as pfrl_iqn_embed_fwd; every pointer but part is required. */
+int pfrl_iqn_embed_bwd(const float *g, const float *emb, const float *w, const float *b,
+                       const float *psi, float *dpsi, float *dw, float *db, float *part,
+                       int64_t part_floats, int32_t B, int32_t N, int32_t n, int32_t H, void *stream);
+
 /* Ragged gather of sampled episodes for recurrent updates: batch_recurrent_experiences
  * (pfrl/replay_buffer.py:219-287) over EpisodicReplayBuffer.sample_episodes (pfrl/replay_buffers/
  * episodic.py:48-85, windows cut by random_subseq).  An episode is a run of consecutive

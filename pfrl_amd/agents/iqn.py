@@ -7,11 +7,13 @@ captured update are DQN's; the quantile thresholds are drawn with ``torch.rand``
 the agent's device, three draws per update in the reference's order (taus for the
 prediction, taus~ for the greedy action, taus' for the target).  On the GPU everything behind
 the three network passes -- greedy action, Bellman target, the quantile Huber loss of every
-pair, its gradient and the priorities -- is one HIP launch (``pfrl_iqn_loss``); the
+pair, its gradient and the priorities -- is one HIP launch (``pfrl_iqn_loss``), and inside each
+pass the threshold embedding up to ``f`` is another (``pfrl_iqn_embed_fwd``); the
 stock-PyTorch composite is the CPU path and the path of subclasses that override the target
 or loss computation.
 """
 import math
+import os
 
 import torch
 from torch import nn
@@ -56,6 +58,26 @@ class ImplicitQuantileQFunction(nn.Module):
         return _quantile_head(psi_x, self.phi, self.f)
 
 
+def _fused_embedding_linear(psi_x, phi, taus):
+    """The ``nn.Linear`` of ``phi`` where the embedding, its ReLU and the product with ``psi_x`` are
+    one launch (``ops.iqn_embed``, csrc/iqn_embed.hip), else None: ``phi`` exactly
+    ``nn.Sequential(CosineBasisLinear, nn.ReLU)`` of the plain classes (a subclass may compute
+    anything), a plain Linear with a bias, shapes inside the launch's gate.  ``PFRL_IQN_EMBED=0``
+    keeps the statements below."""
+    from pfrl_amd import ops
+
+    if os.environ.get("PFRL_IQN_EMBED", "1") == "0" or not psi_x.is_cuda:
+        return None
+    if type(phi) is not nn.Sequential or len(phi) != 2:
+        return None
+    if type(phi[0]) is not CosineBasisLinear or type(phi[1]) is not nn.ReLU:
+        return None
+    linear = phi[0].linear
+    if type(linear) is not nn.Linear or linear.in_features != phi[0].n_basis_functions:
+        return None
+    return linear if ops.iqn_embed_supported(psi_x, taus, linear) else None
+
+
 def _quantile_head(psi_x, phi, f):
     """The function of the thresholds both Q-function classes return: quantile values of every
     action at ``taus`` (B, n_taus) for the embedded states ``psi_x`` (B, hidden)."""
@@ -63,6 +85,12 @@ def _quantile_head(psi_x, phi, f):
     def evaluate_with_quantile_thresholds(taus):
         batch, hidden = psi_x.shape
         assert taus.ndim == 2 and taus.shape[0] == batch
+        linear = _fused_embedding_linear(psi_x, phi, taus)
+        if linear is not None:
+            from pfrl_amd import ops
+
+            h = f(ops.iqn_embed(psi_x, taus, linear))
+            return QuantileDiscreteActionValue(h.reshape(batch, taus.shape[1], h.shape[-1]))
         phi_taus = phi(taus)
         assert phi_taus.shape == (batch, taus.shape[1], hidden)
         h = f((psi_x.unsqueeze(1) * phi_taus).reshape(-1, hidden))

@@ -4,6 +4,7 @@ Tensors only supply device pointers and the current HIP stream; every
 computation happens in the hand-written gfx950 kernels of pfrl_amd/csrc.
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -1680,6 +1681,77 @@ def iqn_loss(quantiles, action, taus, next_quantiles, next_select, reward, disco
     """-> (loss scalar with grad, per-sample mean quantile Huber loss [B])"""
     return _IQNLoss.apply(quantiles, action, taus, next_quantiles, next_select, reward, discount,
                           terminal, weights, mean)
+
+
+IQN_EMBED_MAX = 64          # thresholds per batch row, and basis functions (csrc/iqn_embed.hip)
+_IQN_EMBED_SLAB_ROWS = 256  # rows of one weight-gradient slab there
+_IQN_I_PI = {}
+
+
+def _iqn_i_pi(n, device):
+    """pi, 2 pi, ... n pi as ``agents.iqn.cosine_basis_functions`` rounds them, once per (n, device)."""
+    key = (n, device)
+    if key not in _IQN_I_PI:
+        _IQN_I_PI[key] = torch.arange(1, n + 1, dtype=torch.float, device=device) * math.pi
+    return _IQN_I_PI[key]
+
+
+class _IQNEmbed(torch.autograd.Function):
+    """psi_x [B, H], taus [B, N], the embedding's Linear(n, H) -> psi * relu(linear(cos(taus i pi)))
+    [B N, H] in one launch; the cosines are kept for the backward only when a gradient is wanted."""
+
+    @staticmethod
+    def forward(ctx, psi_x, taus, weight, bias):
+        (B, H), N, n, dev = psi_x.shape, taus.shape[1], weight.shape[1], psi_x.device
+        train = any(ctx.needs_input_grad)
+        out = torch.empty((B * N, H), dtype=torch.float32, device=dev)
+        emb = torch.empty((B * N, n), dtype=torch.float32, device=dev) if train else None
+        check(_native.lib().pfrl_iqn_embed_fwd(_ptr(taus), _ptr(_iqn_i_pi(n, dev)), _ptr(weight), _ptr(bias),
+                                               _ptr(psi_x), _ptr(out), _ptr(emb), B, N, n, H, _stream()),
+              "iqn_embed_fwd")
+        if train:
+            ctx.save_for_backward(psi_x, weight, bias, emb)
+            ctx.N = N
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        psi_x, weight, bias, emb = ctx.saved_tensors
+        (B, H), N, n, dev = psi_x.shape, ctx.N, weight.shape[1], psi_x.device
+        dpsi, dw, db = torch.empty_like(psi_x), torch.empty_like(weight), torch.empty_like(bias)
+        slabs = -(-B * N // _IQN_EMBED_SLAB_ROWS)
+        floats = slabs * (-(-H * n // 4) * 4 + -(-H // 4) * 4) if slabs > 1 else 0
+        part = torch.empty(floats, dtype=torch.float32, device=dev) if floats else None
+        check(_native.lib().pfrl_iqn_embed_bwd(_ptr(g.contiguous()), _ptr(emb), _ptr(weight), _ptr(bias),
+                                               _ptr(psi_x), _ptr(dpsi), _ptr(dw), _ptr(db), _ptr(part), floats,
+                                               B, N, n, H, _stream()), "iqn_embed_bwd")
+        need = ctx.needs_input_grad
+        return (dpsi if need[0] else None, None, dw if need[2] else None, db if need[3] else None)
+
+
+def iqn_embed_supported(psi_x, taus, linear):
+    """Inside the envelope of :func:`iqn_embed` (csrc/iqn_embed.hip refuses the rest): f32 contiguous
+    CUDA tensors on one device, at most 64 thresholds a row and 64 basis functions, fewer than 2^31
+    output elements, thresholds that are draws (no gradient), a Linear with a bias."""
+    weight, bias = linear.weight, linear.bias
+    ts = (psi_x, taus, weight, bias)
+    if bias is None or not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                               and t.device == psi_x.device for t in ts):
+        return False
+    if psi_x.ndim != 2 or taus.ndim != 2 or taus.shape[0] != psi_x.shape[0] or taus.requires_grad:
+        return False
+    (B, H), N, n = psi_x.shape, taus.shape[1], weight.shape[1]
+    return (weight.shape[0] == H and B >= 1 and H >= 1 and 1 <= N <= IQN_EMBED_MAX
+            and 1 <= n <= IQN_EMBED_MAX and B * N * H < 2 ** 31 and _native.available())
+
+
+def iqn_embed(psi_x, taus, linear):
+    """IQN's quantile head up to ``f``: ``psi_x[:, None] * relu(linear(cos(taus[..., None] * i_pi)))``
+    as rows [B N, H], forward in one HIP launch, backward in two or three (gradients for ``psi_x`` and
+    the Linear; none for ``taus``).  Differentiable once."""
+    assert iqn_embed_supported(psi_x, taus, linear)
+    return _IQNEmbed.apply(psi_x, taus, linear.weight, linear.bias)
 
 
 class _DuelingSoftmax(torch.autograd.Function):
