@@ -25,37 +25,24 @@
 // serves; rows beyond 64 go to blockIdx.y (the weights then come from L2 / MALL).
 //
 // Data movement.  A weight element is used by one workgroup once, so it goes from global memory
-// straight into the MFMA B operand: lane (c = lane & 15, kq = lane >> 4) loads the four floats
-// k0 + 4 kq .. + 3 of its gate row as one 16-byte load and MFMA step i of the block takes element i
-// of every lane's four for both operands (any bijection of k serves a reduction).  x / h rows go the
-// same way into the A operand; every workgroup re-reads them (32 KB at 8 rows), which stays in L2.
+// straight into the MFMA B operand, the lane's gate row in the load form of csrc/recurrent_mfma.h.
+// x / h rows go the same way into the A operand; every workgroup re-reads them (32 KB at 8 rows),
+// which stays in L2.
 // LDS holds only the partial tiles, [16 waves][16 MT rows][17] floats, folded in wave order by the
 // thread that then runs the gate arithmetic of its (row, unit) and stores h' (twice where the caller
 // wants the step's output next to the carried state): no gates tensor in HBM, no atomics, no
 // scratch, no second launch, the same bits on every launch.  A wave that holds only h blocks adds
 // exact zeros to n_x and the other way round, so the fold needs no case distinction.
 //
-// Tails are the kernel's: columns beyond I / H enter as zeros (clamped address, masked value), rows
-// beyond N and units beyond H repeat the last valid one and are not stored; h0 == NULL drops the h
-// blocks from the range altogether (n_h is then b_hn alone).
-#include "common.h"
+// Tails are the kernel's, by the rules of csrc/recurrent_mfma.h (columns beyond I / H, rows beyond
+// N, units beyond H); h0 == NULL drops the h blocks from the range altogether (n_h is then b_hn
+// alone).
+#include "recurrent_mfma.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// (as csrc/lstm.hip: the fixed-order sums are not to change form with the compiler)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PFRL_NO_PACKED_FP32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define PFRL_NO_PACKED_FP32
-#endif
-
 constexpr int kUnits = 4;           // hidden units of a workgroup (16 columns: r, z, n_x, n_h of each)
 constexpr int kWaves = 16;          // waves of a workgroup, each a share of the reduction
-constexpr int kRowsPerWg = 64;      // 4 M-tiles
-constexpr int kMaxRows = 256;       // blockIdx.y <= 4: the admitted envelope
-constexpr int kPad = 17;            // LDS row stride of a partial tile
 enum { kR = 0, kZ = 1, kNx = 2, kNh = 3 };
 
 struct GruArgs {
@@ -63,18 +50,6 @@ struct GruArgs {
     float *h1, *y;
     int N, I, H;
 };
-
-// Four consecutive floats k .. k + 3 of a matrix row of K columns; addresses beyond the row are
-// clamped into it and the caller zeroes those elements when it uses them.  VEC: K % 4 == 0 and the
-// row starts on 16 bytes (k is always a multiple of 4), so the four are in or out together.
-template <bool VEC>
-__device__ __forceinline__ float4 load4(const float *__restrict__ row, int k, int K) {
-    if (VEC) return *reinterpret_cast<const float4 *>(row + min(k, K - 4));
-    return make_float4(row[min(k, K - 1)], row[min(k + 1, K - 1)], row[min(k + 2, K - 1)],
-                       row[min(k + 3, K - 1)]);
-}
-
-__device__ __forceinline__ float sigmoidf(float v) { return 1.f / (1.f + expf(-v)); }
 
 template <int MT, int UNR, bool VEC>
 __global__ __launch_bounds__(kWaves * 64) PFRL_NO_PACKED_FP32 void k_gru_cell_fwd(GruArgs a) {
@@ -87,51 +62,14 @@ __global__ __launch_bounds__(kWaves * 64) PFRL_NO_PACKED_FP32 void k_gru_cell_fw
     // n_x and n_h are both gate 2, one in W_ih and one in W_hh
     const unsigned grow = (unsigned)(min(kind, 2) * H + min(j0 + (c16 & 3), H - 1));
     unsigned arow[MT];                                     // this lane's x / h0 rows
-#pragma unroll
-    for (int t = 0; t < MT; ++t) arow[t] = (unsigned)min(row0 + 16 * t + c16, N - 1);
+    clamp_rows(arow, row0, c16, N - 1);
 
-    const int nb0 = (I + 15) >> 4, nb = nb0 + (a.h0 != nullptr ? (H + 15) >> 4 : 0);
-    const int b_begin = wave * nb / kWaves, b_end = (wave + 1) * nb / kWaves;
     f32x4 acc[MT];
+    // the candidate's two columns each own one part of the range: nothing is loaded in the other
+    reduce_concat<kWaves, UNR, VEC>(acc, a.x, a.h0, a.w_ih, a.w_hh, I, H, grow, arow, wave, kq,
+                                    [kind](bool hh) { return kind != (hh ? kNx : kNh); });
 #pragma unroll
-    for (int t = 0; t < MT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int b = b_begin; b < b_end; b += UNR) {
-        float4 w[UNR], v[UNR][MT];
-        int left[UNR];                                     // columns of the row from this lane's k on
-#pragma unroll
-        for (int j = 0; j < UNR; ++j) {
-            const int bb = min(b + j, b_end - 1);          // (clamped: a short last trip repeats, as zeros)
-            const bool hh = bb >= nb0;                     // (uniform) which part of the concatenated range
-            const int K = hh ? H : I, k = 16 * (bb - (hh ? nb0 : 0)) + 4 * kq;
-            const float *__restrict__ wm = hh ? a.w_hh : a.w_ih;
-            const float *__restrict__ am = hh ? a.h0 : a.x;
-            left[j] = b + j < b_end ? K - k : 0;
-            // the candidate's two columns each own one part of the range: nothing is loaded in the other
-            w[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (kind != (hh ? kNx : kNh)) w[j] = load4<VEC>(wm + (size_t)grow * K, k, K);
-#pragma unroll
-            for (int t = 0; t < MT; ++t) v[j][t] = load4<VEC>(am + (size_t)arow[t] * K, k, K);
-        }
-#pragma unroll
-        for (int j = 0; j < UNR; ++j) {
-            const float wv[4] = {left[j] > 0 ? w[j].x : 0.f, left[j] > 1 ? w[j].y : 0.f,
-                                 left[j] > 2 ? w[j].z : 0.f, left[j] > 3 ? w[j].w : 0.f};
-#pragma unroll
-            for (int t = 0; t < MT; ++t) {
-                const float av[4] = {left[j] > 0 ? v[j][t].x : 0.f, left[j] > 1 ? v[j][t].y : 0.f,
-                                     left[j] > 2 ? v[j][t].z : 0.f, left[j] > 3 ? v[j][t].w : 0.f};
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], wv[i], acc[t], 0, 0, 0);
-            }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < MT; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)       // accumulator layout: row = 4 (lane >> 4) + i, column = lane & 15
-            part[wave][16 * t + 4 * kq + i][c16] = acc[t][i];
+    for (int t = 0; t < MT; ++t) store_partial(part, wave, t, acc[t], c16, kq);
     __syncthreads();
 
     // one thread per (row, unit): the four columns folded in wave order, then the gate arithmetic
@@ -143,9 +81,7 @@ __global__ __launch_bounds__(kWaves * 64) PFRL_NO_PACKED_FP32 void k_gru_cell_fw
     float g[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        float s = part[0][r][4 * q + u];
-#pragma unroll
-        for (int wv = 1; wv < kWaves; ++wv) s += part[wv][r][4 * q + u];
+        float s = fold_waves(part, r, 4 * q + u);
         // r and z take both biases, n_x only b_in, n_h only b_hn
         if (a.b_ih != nullptr && q != kNh) s += a.b_ih[q * H + j];
         if (a.b_hh != nullptr && q != kNx) s += a.b_hh[min(q, 2) * H + j];
@@ -157,16 +93,6 @@ __global__ __launch_bounds__(kWaves * 64) PFRL_NO_PACKED_FP32 void k_gru_cell_fw
     a.h1[o] = h1;
     if (a.y != nullptr) a.y[o] = h1;      // the step's output next to the carried state: two buffers, as nn.GRU's
 }
-
-template <int MT, int UNR>
-void launch(const GruArgs &a, bool vec, dim3 grid, hipStream_t st) {
-    if (vec)
-        hipLaunchKernelGGL((k_gru_cell_fwd<MT, UNR, true>), grid, dim3(kWaves * 64), 0, st, a);
-    else
-        hipLaunchKernelGGL((k_gru_cell_fwd<MT, UNR, false>), grid, dim3(kWaves * 64), 0, st, a);
-}
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -185,11 +111,9 @@ extern "C" int pfrl_gru_cell_fwd(const float *x, const float *h0, const float *w
                      (h0 == nullptr || aligned16(h0));
     const dim3 grid((H + kUnits - 1) / kUnits, (N + kRowsPerWg - 1) / kRowsPerWg);
     hipStream_t st = (hipStream_t)stream;
-    if (N <= 16)
-        launch<1, 4>(a, vec, grid, st);
-    else if (N <= 32)
-        launch<2, 4>(a, vec, grid, st);
-    else
-        launch<4, 2>(a, vec, grid, st);
+    with_tiles(N, vec, [&](auto mt, auto v) {
+        constexpr int MT = decltype(mt)::value, UNR = MT == 4 ? 2 : 4;     // blocks per load trip
+        hipLaunchKernelGGL((k_gru_cell_fwd<MT, UNR, decltype(v)::value>), grid, dim3(kWaves * 64), 0, st, a);
+    });
     PFRL_LAUNCH_CHECK();
 }

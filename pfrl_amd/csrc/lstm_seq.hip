@@ -35,33 +35,17 @@
 // one workgroup once.  A transpose through LDS would add a store, a barrier and a load per element
 // for no reuse, so the loads stay direct.  No transposed copy of the weights exists anywhere.
 //
-// No atomics, one fixed order of every sum: the same inputs give the same bits on every launch.
-// Tails: k beyond the reduction enters as zeros (clamped address, masked value), rows and units
-// beyond the step's repeat the last valid one and are not stored.
-#include <vector>
-
-#include "common.h"
+// Load form, tails and fold order are csrc/recurrent_mfma.h's: no atomics, one fixed order of every
+// sum, the same inputs give the same bits on every launch.
+#include "recurrent_mfma.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-// (as csrc/lstm.hip: the fixed-order sums are not to change form with the compiler)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PFRL_NO_PACKED_FP32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define PFRL_NO_PACKED_FP32
-#endif
 
 constexpr int kFwdUnits = 4;        // hidden units of a forward workgroup (16 gate columns)
 constexpr int kFwdWaves = 8;
 constexpr int kBwdUnits = 16;       // hidden units of a backward workgroup (16 columns of dh)
 constexpr int kBwdWaves = 16;
 constexpr int kUnr = 4;             // blocks of 16 k per load trip
-constexpr int kRowsPerWg = 64;      // 4 M-tiles
-constexpr int kMaxRows = 256;       // blockIdx.y <= 4
-constexpr int kPad = 17;            // LDS row stride of a partial tile
 
 struct SeqFwdArgs {
     const float *p, *hprev, *cprev, *w_hh;     // p, hprev, cprev: rows of this step / the step before
@@ -76,36 +60,6 @@ struct SeqBwdArgs {
     int n_s, n_prev, H;                        // rows of step s (0 at s = T) and s - 1 (0 at s = 0)
 };
 
-// Four consecutive floats k .. k + 3 of a row of K columns, clamped into the row; the caller zeroes
-// what lies beyond it.  VEC: K % 4 == 0 and the row starts on 16 bytes.
-template <bool VEC>
-__device__ __forceinline__ float4 load4(const float *__restrict__ row, int k, int K) {
-    if (VEC) return *reinterpret_cast<const float4 *>(row + min(k, K - 4));
-    return make_float4(row[min(k, K - 1)], row[min(k + 1, K - 1)], row[min(k + 2, K - 1)],
-                       row[min(k + 3, K - 1)]);
-}
-
-__device__ __forceinline__ float sigmoidf(float v) { return 1.f / (1.f + expf(-v)); }
-
-// One load trip's MFMAs: kUnr blocks, element i of every lane's four for both operands.
-template <int MT>
-__device__ __forceinline__ void mfma_trip(f32x4 (&acc)[MT], const float4 (&w)[kUnr],
-                                          const float4 (&v)[kUnr][MT], const int (&left)[kUnr]) {
-#pragma unroll
-    for (int j = 0; j < kUnr; ++j) {
-        const float wv[4] = {left[j] > 0 ? w[j].x : 0.f, left[j] > 1 ? w[j].y : 0.f,
-                             left[j] > 2 ? w[j].z : 0.f, left[j] > 3 ? w[j].w : 0.f};
-#pragma unroll
-        for (int t = 0; t < MT; ++t) {
-            const float av[4] = {left[j] > 0 ? v[j][t].x : 0.f, left[j] > 1 ? v[j][t].y : 0.f,
-                                 left[j] > 2 ? v[j][t].z : 0.f, left[j] > 3 ? v[j][t].w : 0.f};
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], wv[i], acc[t], 0, 0, 0);
-        }
-    }
-}
-
 template <int MT, bool VEC>
 __global__ __launch_bounds__(kFwdWaves * 64) PFRL_NO_PACKED_FP32 void k_lstm_seq_step_fwd(SeqFwdArgs a) {
     __shared__ float part[kFwdWaves][MT * 16][kPad];
@@ -115,11 +69,10 @@ __global__ __launch_bounds__(kFwdWaves * 64) PFRL_NO_PACKED_FP32 void k_lstm_seq
     const int j0 = blockIdx.x * kFwdUnits, row0 = blockIdx.y * kRowsPerWg;
     const unsigned grow = (unsigned)((c16 >> 2) * H + min(j0 + (c16 & 3), H - 1));   // this lane's gate row
     unsigned arow[MT];                                                              // ... and its h rows
-#pragma unroll
-    for (int t = 0; t < MT; ++t) arow[t] = (unsigned)min(row0 + 16 * t + c16, N - 1);
+    clamp_rows(arow, row0, c16, N - 1);
 
     const int nb = a.hprev != nullptr ? (H + 15) >> 4 : 0;      // no carried state: no reduction at all
-    const int b_begin = wave * nb / kFwdWaves, b_end = (wave + 1) * nb / kFwdWaves;
+    const int b_begin = share_begin<kFwdWaves>(wave, nb), b_end = share_begin<kFwdWaves>(wave + 1, nb);
     f32x4 acc[MT];
 #pragma unroll
     for (int t = 0; t < MT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -134,13 +87,10 @@ __global__ __launch_bounds__(kFwdWaves * 64) PFRL_NO_PACKED_FP32 void k_lstm_seq
 #pragma unroll
             for (int t = 0; t < MT; ++t) v[j][t] = load4<VEC>(a.hprev + (size_t)arow[t] * H, k, H);
         }
-        mfma_trip<MT>(acc, w, v, left);
+        mfma_trip(acc, w, v, left);
     }
 #pragma unroll
-    for (int t = 0; t < MT; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)       // accumulator layout: row = 4 (lane >> 4) + i, column = lane & 15
-            part[wave][16 * t + 4 * kq + i][c16] = acc[t][i];
+    for (int t = 0; t < MT; ++t) store_partial(part, wave, t, acc[t], c16, kq);
     __syncthreads();
 
     // one thread per (row, unit): the four gates folded in wave order, then the cell update
@@ -151,12 +101,7 @@ __global__ __launch_bounds__(kFwdWaves * 64) PFRL_NO_PACKED_FP32 void k_lstm_seq
     if (n >= N || j >= H) return;
     float g[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float s = part[0][r][4 * q + u];
-#pragma unroll
-        for (int wv = 1; wv < kFwdWaves; ++wv) s += part[wv][r][4 * q + u];
-        g[q] = s + a.p[(size_t)n * 4 * H + q * H + j];
-    }
+    for (int q = 0; q < 4; ++q) g[q] = fold_waves(part, r, 4 * q + u) + a.p[(size_t)n * 4 * H + q * H + j];
     const size_t o = (size_t)n * H + j;
     const float gi = sigmoidf(g[0]), gf = sigmoidf(g[1]), gg = tanhf(g[2]), go = sigmoidf(g[3]);
     const float c1 = a.cprev != nullptr ? gf * a.cprev[o] + gi * gg : gi * gg;
@@ -179,12 +124,11 @@ __global__ __launch_bounds__(kBwdWaves * 64) PFRL_NO_PACKED_FP32 void k_lstm_seq
     const int j0 = blockIdx.x * kBwdUnits, row0 = blockIdx.y * kRowsPerWg;
     const int bcol = min(j0 + c16, H - 1);                      // this lane's column of W_hh
     unsigned arow[MT];                                          // ... and its dA rows
-#pragma unroll
-    for (int t = 0; t < MT; ++t) arow[t] = (unsigned)max(min(row0 + 16 * t + c16, Ns - 1), 0);
+    clamp_rows(arow, row0, c16, max(Ns - 1, 0));                // (s = T has no rows and no reduction)
 
     // (a) dh_prev = dA_s W_hh: K = 4H over the waves, accumulated in f64 (see the head of the file)
     const int nb = Ns > 0 ? (K + 15) >> 4 : 0;
-    const int b_begin = wave * nb / kBwdWaves, b_end = (wave + 1) * nb / kBwdWaves;
+    const int b_begin = share_begin<kBwdWaves>(wave, nb), b_end = share_begin<kBwdWaves>(wave + 1, nb);
     f64x4 acc[MT];
 #pragma unroll
     for (int t = 0; t < MT; ++t) acc[t] = f64x4{0., 0., 0., 0.};
@@ -201,25 +145,10 @@ __global__ __launch_bounds__(kBwdWaves * 64) PFRL_NO_PACKED_FP32 void k_lstm_seq
 #pragma unroll
             for (int t = 0; t < MT; ++t) v[j][t] = load4<true>(a.da_s + (size_t)arow[t] * K, k, K);   // (K = 4H: always 16-byte rows)
         }
-#pragma unroll
-        for (int j = 0; j < kUnr; ++j) {
-            const float wv[4] = {left[j] > 0 ? w[j].x : 0.f, left[j] > 1 ? w[j].y : 0.f,
-                                 left[j] > 2 ? w[j].z : 0.f, left[j] > 3 ? w[j].w : 0.f};
-#pragma unroll
-            for (int t = 0; t < MT; ++t) {
-                const float av[4] = {left[j] > 0 ? v[j][t].x : 0.f, left[j] > 1 ? v[j][t].y : 0.f,
-                                     left[j] > 2 ? v[j][t].z : 0.f, left[j] > 3 ? v[j][t].w : 0.f};
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[i], (double)wv[i], acc[t], 0, 0, 0);
-            }
-        }
+        mfma_trip(acc, w, v, left);
     }
 #pragma unroll
-    for (int t = 0; t < MT; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)       // f64 accumulator layout: row = (lane >> 4) + 4 i, column = lane & 15
-            part[wave][16 * t + kq + 4 * i][c16] = acc[t][i];
+    for (int t = 0; t < MT; ++t) store_partial(part, wave, t, acc[t], c16, kq);
     __syncthreads();
 
     // one thread per (row, unit): dh_prev folded in wave order and rounded once, then (b) the gradient of step s - 1
@@ -228,10 +157,7 @@ __global__ __launch_bounds__(kBwdWaves * 64) PFRL_NO_PACKED_FP32 void k_lstm_seq
     if (r >= MT * 16) return;
     const int n = row0 + r, j = j0 + u;
     if (j >= H) return;
-    double sum = part[0][r][u];
-#pragma unroll
-    for (int wv = 1; wv < kBwdWaves; ++wv) sum += part[wv][r][u];
-    const float dhp = (float)sum;
+    const float dhp = (float)fold_waves(part, r, u);
     const size_t o = (size_t)n * H + j;
     if (Np == 0) {                        // s = 0: what is carried is the gradient of the initial state
         if (n < Ns) a.dh0[o] = dhp;       // (dc0 is dc_carry itself)
@@ -253,35 +179,7 @@ __global__ __launch_bounds__(kBwdWaves * 64) PFRL_NO_PACKED_FP32 void k_lstm_seq
     a.dc_carry[o] = dc * gf;
 }
 
-template <int MT>
-void launch_fwd(const SeqFwdArgs &a, bool vec, dim3 grid, hipStream_t st) {
-    if (vec)
-        hipLaunchKernelGGL((k_lstm_seq_step_fwd<MT, true>), grid, dim3(kFwdWaves * 64), 0, st, a);
-    else
-        hipLaunchKernelGGL((k_lstm_seq_step_fwd<MT, false>), grid, dim3(kFwdWaves * 64), 0, st, a);
-}
-
-template <int MT>
-void launch_bwd(const SeqBwdArgs &a, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL((k_lstm_seq_step_bwd<MT>), grid, dim3(kBwdWaves * 64), 0, st, a);
-}
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-// The envelope both entries share; fills off[0 .. T] (first row of every step, and R).
-const char *check_sizes(const int32_t *bs, int32_t T, int32_t H, std::vector<int64_t> &off) {
-    if (bs == nullptr) return "null batch_sizes";
-    if (T < 1 || H < 1) return "at least one time step and one hidden unit";
-    off.assign((size_t)T + 1, 0);
-    for (int t = 0; t < T; ++t) {
-        if (bs[t] < 1 || (t > 0 && bs[t] > bs[t - 1])) return "batch sizes must be >= 1 and non-increasing";
-        off[t + 1] = off[t] + bs[t];
-    }
-    if (bs[0] > kMaxRows) return "at most 256 rows per step";
-    if (off[T] * 4 * H >= ((int64_t)1 << 31) || 4 * (int64_t)H * H >= ((int64_t)1 << 31))
-        return "2^31 gate elements or more";
-    return nullptr;
-}
+const char *const kTooLarge = "2^31 gate elements or more";
 
 }  // namespace
 
@@ -290,7 +188,7 @@ extern "C" int pfrl_lstm_seq_fwd(const float *p, const float *h0, const float *c
                                  const int32_t *batch_sizes, int32_t T, int32_t H, void *stream) {
     PFRL_CHECK_ARG(p && w_hh && y && c && hn && cn, "pfrl_lstm_seq_fwd: null pointer");
     std::vector<int64_t> off;
-    const char *bad = check_sizes(batch_sizes, T, H, off);
+    const char *bad = check_sizes(batch_sizes, T, H, 4, kTooLarge, off);
     PFRL_CHECK_ARG(bad == nullptr, bad);
     hipStream_t st = (hipStream_t)stream;
     for (int t = 0; t < T; ++t) {
@@ -301,12 +199,10 @@ extern "C" int pfrl_lstm_seq_fwd(const float *p, const float *h0, const float *c
                            n, t + 1 < T ? batch_sizes[t + 1] : 0, H};
         const bool vec = H % 4 == 0 && aligned16(w_hh) && aligned16(hprev);
         const dim3 grid((H + kFwdUnits - 1) / kFwdUnits, (n + kRowsPerWg - 1) / kRowsPerWg);
-        if (n <= 16)
-            launch_fwd<1>(a, vec, grid, st);
-        else if (n <= 32)
-            launch_fwd<2>(a, vec, grid, st);
-        else
-            launch_fwd<4>(a, vec, grid, st);
+        with_tiles(n, vec, [&](auto mt, auto v) {
+            hipLaunchKernelGGL((k_lstm_seq_step_fwd<decltype(mt)::value, decltype(v)::value>), grid,
+                               dim3(kFwdWaves * 64), 0, st, a);
+        });
     }
     PFRL_LAUNCH_CHECK();
 }
@@ -317,7 +213,7 @@ extern "C" int pfrl_lstm_seq_bwd(const float *dy, const float *dhn, const float 
                                  int32_t H, void *stream) {
     PFRL_CHECK_ARG(dy && w_hh && gates && c && da && dc0, "pfrl_lstm_seq_bwd: null pointer");
     std::vector<int64_t> off;
-    const char *bad = check_sizes(batch_sizes, T, H, off);
+    const char *bad = check_sizes(batch_sizes, T, H, 4, kTooLarge, off);
     PFRL_CHECK_ARG(bad == nullptr, bad);
     hipStream_t st = (hipStream_t)stream;
     PFRL_CHECK_ARG(aligned16(da), "pfrl_lstm_seq_bwd: da must start on 16 bytes");   // (then every row of 4H floats does)
@@ -329,12 +225,9 @@ extern "C" int pfrl_lstm_seq_bwd(const float *dy, const float *dhn, const float 
                            da + op * 4 * H, dc0, dh0, n_s, n_prev, H};
         const int rows = s > 0 ? n_prev : n_s;
         const dim3 grid((H + kBwdUnits - 1) / kBwdUnits, (rows + kRowsPerWg - 1) / kRowsPerWg);
-        if (rows <= 16)
-            launch_bwd<1>(a, grid, st);
-        else if (rows <= 32)
-            launch_bwd<2>(a, grid, st);
-        else
-            launch_bwd<4>(a, grid, st);
+        with_tiles(rows, true, [&](auto mt, auto) {          // (dA rows are 4H floats: always 16-byte loads)
+            hipLaunchKernelGGL((k_lstm_seq_step_bwd<decltype(mt)::value>), grid, dim3(kBwdWaves * 64), 0, st, a);
+        });
     }
     PFRL_LAUNCH_CHECK();
 }

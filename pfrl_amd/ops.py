@@ -1818,16 +1818,30 @@ def lstm_cell_step(x, h0, c0, w_ih, w_hh, b_ih, b_hh, want_output=False):
     return (h1, c1, y) if want_output else (h1, c1)
 
 
-def lstm_sequence_supported(batch_sizes, I, H):
-    """Packed shapes inside the envelope of :func:`lstm_sequence` (csrc/lstm_seq.hip refuses the
-    others): ``batch_sizes`` a sequence of ints, non-increasing and >= 1, at most 256 rows a step."""
+def _packed_sequence_supported(batch_sizes, I, H):
+    # (both cell types keep 4H floats a row, so one bound serves the LSTM and the GRU)
     b = [int(n) for n in batch_sizes]
     return (len(b) >= 1 and b[-1] >= 1 and b[0] <= LSTM_CELL_MAX_N and all(m >= n for m, n in zip(b, b[1:]))
             and I >= 1 and H >= 1 and 4 * H * max(sum(b), I, H) < 2 ** 31)
 
 
+def lstm_sequence_supported(batch_sizes, I, H):
+    """Packed shapes inside the envelope of :func:`lstm_sequence` (csrc/lstm_seq.hip refuses the
+    others): ``batch_sizes`` a sequence of ints, non-increasing and >= 1, at most 256 rows a step."""
+    return _packed_sequence_supported(batch_sizes, I, H)
+
+
 def _sizes_array(batch_sizes):
     return (ctypes.c_int32 * len(batch_sizes))(*batch_sizes)     # a HOST array: no synchronisation
+
+
+def _previous_hidden(y, h0, batch_sizes):
+    """h_{t-1} of every packed row: the initial state (zeros for None), then the output rows one step back."""
+    b, off = batch_sizes, [0]
+    for n in b:
+        off.append(off[-1] + n)
+    first = y.new_zeros((b[0], y.shape[1])) if h0 is None else h0
+    return torch.cat([first] + [y[off[t - 1]:off[t - 1] + b[t]] for t in range(1, len(b))])
 
 
 def lstm_seq_forward(p, batch_sizes, h0, c0, w_hh, want_gates):
@@ -1889,14 +1903,7 @@ class _LSTMSequence(torch.autograd.Function):
         da, dh0, dc0 = lstm_seq_backward(dy, dhn, dcn, w_hh, gates, c, c0, b, want_dh0=need[1])
         dx = da @ w_ih if need[0] else None
         dw_ih = da.t() @ x if need[3] else None
-        dw_hh = None
-        if need[4]:     # h_{t-1} of every row: the initial state, then the output rows one step back
-            off = [0]
-            for n in b:
-                off.append(off[-1] + n)
-            first = y.new_zeros((b[0], y.shape[1])) if h0 is None else h0
-            h_prev = torch.cat([first] + [y[off[t - 1]:off[t - 1] + b[t]] for t in range(1, len(b))])
-            dw_hh = da.t() @ h_prev
+        dw_hh = da.t() @ _previous_hidden(y, h0, b) if need[4] else None
         db = da.sum(0) if (need[5] or need[6]) else None
         return (dx, dh0, dc0 if need[2] else None, dw_ih, dw_hh, db if need[5] else None,
                 db if need[6] else None, None)
@@ -1945,9 +1952,7 @@ def gru_cell_step(x, h0, w_ih, w_hh, b_ih, b_hh, want_output=False):
 def gru_sequence_supported(batch_sizes, I, H):
     """Packed shapes inside the envelope of :func:`gru_sequence` (csrc/gru_seq.hip refuses the
     others): ``batch_sizes`` a sequence of ints, non-increasing and >= 1, at most 256 rows a step."""
-    b = [int(n) for n in batch_sizes]
-    return (len(b) >= 1 and b[-1] >= 1 and b[0] <= LSTM_CELL_MAX_N and all(m >= n for m, n in zip(b, b[1:]))
-            and I >= 1 and H >= 1 and 4 * H * max(sum(b), I, H) < 2 ** 31)
+    return _packed_sequence_supported(batch_sizes, I, H)
 
 
 def gru_seq_forward(p, batch_sizes, h0, w_hh, b_hn, want_saved):
@@ -2016,14 +2021,7 @@ class _GRUSequence(torch.autograd.Function):
         dp, dq, dh0 = gru_seq_backward(dy, dhn, w_hh, saved, y, h0, b, want_dh0=need[1])
         dx = dp @ w_ih if need[0] else None
         dw_ih = dp.t() @ x if need[2] else None
-        dw_hh = None
-        if need[3]:     # h_{t-1} of every row: the initial state, then the output rows one step back
-            off = [0]
-            for n in b:
-                off.append(off[-1] + n)
-            first = y.new_zeros((b[0], y.shape[1])) if h0 is None else h0
-            h_prev = torch.cat([first] + [y[off[t - 1]:off[t - 1] + b[t]] for t in range(1, len(b))])
-            dw_hh = dq.t() @ h_prev
+        dw_hh = dq.t() @ _previous_hidden(y, h0, b) if need[3] else None
         return (dx, dh0, dw_ih, dw_hh, dp.sum(0) if need[4] else None, dq.sum(0) if need[5] else None, None)
 
 
