@@ -1163,6 +1163,40 @@ int pfrl_iqn_embed_bwd(const float *g, const float *emb, const float *w, const f
                        const float *psi, float *dpsi, float *dw, float *db, float *part,
                        int64_t part_floats, int32_t B, int32_t N, int32_t n, int32_t H, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Whole small MLPs as one launch (csrc/mlp.hip): the Linear(obs, 64), Tanh, Linear(64, 64), Tanh,
+ * Linear(64, A or 1) networks of the on-policy continuous-control agents, forward in one launch and
+ * backward in one (two above one workgroup: the slabs' fold).  f32 in, f32 accumulate.
+ * Envelope: 1 <= n_layers <= 3 Linear layers with bias, the same activation (PFRL_MLP_TANH or
+ * PFRL_MLP_RELU) behind every layer but the last; 1 <= in_features <= 512; every width 1 .. 64;
+ * 1 <= M <= 65536 rows; n_nets 1 or 2 networks of the same depth on the same x [M][in_features].
+ * Per network k and layer l the host arrays hold w[3 k + l] ([width][fan_in], as nn.Linear),
+ * b[3 k + l], widths[3 k + l], and act[k]; save / saved[2 k + l] is the output of hidden layer l
+ * ([M][width], after the activation), y[k] / dy[k] are [M][last width].  Host arrays are read during
+ * the call only (the launches capture into a graph).
+ * pfrl_mlp_fwd: save may be NULL, and so may its entries (no gradient wanted).  small_m: up to this
+ *   many rows take the 16-row tile program, more the 64-row one (negative: the default, 512).  The bits
+ *   of an output row depend on that row and the parameters only: not on M, the row's position, the tile
+ *   program or n_nets.
+ * pfrl_mlp_bwd: dx (or dx[k]) may be NULL: no input gradient.  grads[k] receives network k's gradient
+ *   packed as [W_0 | b_0 | W_1 | b_1 | ...], every segment padded (with zeros) to a multiple of 4
+ *   floats, P floats in all.  pfrl_mlp_bwd_slabs(M) == 1: one launch, slab_ws and slab_stride are
+ *   ignored.  Otherwise slab_ws[k] is a workspace of pfrl_mlp_bwd_slabs(M) slabs, slab_stride >= P
+ *   floats apart (a multiple of 4); a second launch behind the same call adds the slabs in slab order
+ *   in f64 and rounds once into grads[k].  Fixed summation order, no atomics.
+ * Outside the envelope, null or misaligned pointers: PFRL_ERR_ARG, nothing is written.  n_nets == 0 is
+ * the empty launch: 0, nothing is written. */
+#define PFRL_MLP_TANH 0
+#define PFRL_MLP_RELU 1
+int pfrl_mlp_fwd(const float *x, int32_t M, int32_t in_features, int32_t n_layers, int32_t n_nets,
+                 const float *const *w, const float *const *b, const int32_t *widths, const int32_t *act,
+                 float *const *save, float *const *y, int32_t small_m, void *stream);
+int pfrl_mlp_bwd_slabs(int32_t M);
+int pfrl_mlp_bwd(const float *x, int32_t M, int32_t in_features, int32_t n_layers, int32_t n_nets,
+                 const float *const *w, const int32_t *widths, const int32_t *act,
+                 const float *const *saved, const float *const *dy, float *const *dx, float *const *grads,
+                 float *const *slab_ws, int64_t slab_stride, void *stream);
+
 /* Ragged gather of sampled episodes for recurrent updates: batch_recurrent_experiences
  * (pfrl/replay_buffer.py:219-287) over EpisodicReplayBuffer.sample_episodes (pfrl/replay_buffers/
  * episodic.py:48-85, windows cut by random_subseq).  An episode is a run of consecutive

@@ -12,9 +12,16 @@ import torch
 from torch import nn
 
 from pfrl_amd.nn import Branched
+from pfrl_amd.nn.mfma_linear import _FusedBranched, _FusedMlpSequential
 from pfrl_amd.ops import GAUSSIAN_MAX_A
 from pfrl_amd.policies import (GaussianHeadWithFixedCovariance,
                                GaussianHeadWithStateIndependentCovariance, SoftmaxCategoricalHead)
+
+
+# the plain containers, and what ``nn.mfma_linear._fuse_small_mlps`` makes of them (same children; a view
+# of one keeps its class, so a head-less view runs its MLP as one launch too)
+_SEQUENTIAL = (nn.Sequential, _FusedMlpSequential)
+_BRANCHED = (Branched, _FusedBranched)
 
 
 def _view(module, children):
@@ -55,10 +62,10 @@ def softmax_actor_critic(model):
     Linear(K, A <= 31), SoftmaxCategoricalHead()), Linear(K, 1)))`` -- the reference's example network
     (examples/atari/train_ppo_ale.py:247-264); ``body``: the model without its last child."""
     if not (isinstance(model, nn.Sequential) and len(model) >= 2
-            and type(model[len(model) - 1]) is Branched):
+            and type(model[len(model) - 1]) in _BRANCHED):
         return None
     kids = list(model[len(model) - 1].child_modules)
-    if not (len(kids) == 2 and type(kids[0]) is nn.Sequential and len(kids[0]) == 2):
+    if not (len(kids) == 2 and type(kids[0]) in _SEQUENTIAL and len(kids[0]) == 2):
         return None
     pol, head, val = kids[0][0], kids[0][1], kids[1]
     if not (_softmax_layer_ok(pol, head) and isinstance(val, nn.Linear) and val.out_features == 1
@@ -70,7 +77,7 @@ def softmax_actor_critic(model):
 def softmax_policy(model):
     """(body, policy layer) when ``model`` is ``Sequential(body..., Linear(K, A <= 31),
     SoftmaxCategoricalHead())``, a non-empty body, float32 parameters."""
-    if type(model) is not nn.Sequential or len(model) < 3:
+    if type(model) not in _SEQUENTIAL or len(model) < 3:
         return None
     pol, head = model[len(model) - 2], model[len(model) - 1]
     if not (_softmax_layer_ok(pol, head) and _all_f32(model)):
@@ -99,7 +106,7 @@ class GaussianSplit(NamedTuple):
 def _headless_gaussian_policy(policy):
     """(``policy`` up to its last Linear, head, A) when ``policy`` is ``Sequential(..., Linear(., A <= 32),
     head)`` with one of the two heads whose scale does not depend on the state."""
-    if type(policy) is not nn.Sequential or len(policy) < 2:
+    if type(policy) not in _SEQUENTIAL or len(policy) < 2:
         return None
     pol, head = policy[len(policy) - 2], policy[len(policy) - 1]
     if type(head) not in (GaussianHeadWithStateIndependentCovariance, GaussianHeadWithFixedCovariance):
@@ -131,10 +138,10 @@ def gaussian_actor_critic(model, device):
     ``GaussianHeadWithStateIndependentCovariance`` (spherical or diagonal, any ``var_func``) or a
     ``GaussianHeadWithFixedCovariance``, all parameters float32.  ``view(x)`` is ``(mean [M, A],
     value [M, 1])``; a fixed scale is put on ``device``."""
-    if type(model) is Branched:
+    if type(model) in _BRANCHED:
         branched = model
     elif (isinstance(model, nn.Sequential) and len(model) >= 2
-            and type(model[len(model) - 1]) is Branched):
+            and type(model[len(model) - 1]) in _BRANCHED):
         branched = model[len(model) - 1]
     else:
         return None

@@ -60,6 +60,9 @@ class A2C(agent.AttributeSavingMixin, agent.BatchAgent):
             assert torch.cuda.is_available()
             self.device = torch.device("cuda:{}".format(gpu))
             self.model.to(self.device)
+            from pfrl_amd.nn.mfma_linear import _fuse_small_mlps
+
+            _fuse_small_mlps(self.model)       # small tanh / ReLU MLPs: one launch each way
             from pfrl_amd import _native
 
             _native.lib()

@@ -428,6 +428,9 @@ class PPO(agent.AttributeSavingMixin, agent.BatchAgent):
             assert torch.cuda.is_available()
             self.device = torch.device("cuda:{}".format(gpu))
             self.model.to(self.device)
+            from pfrl_amd.nn.mfma_linear import _fuse_small_mlps
+
+            _fuse_small_mlps(self.model)       # small tanh / ReLU MLPs: one launch each way
             if self.obs_normalizer is not None:
                 self.obs_normalizer.to(self.device)
             from pfrl_amd import _native

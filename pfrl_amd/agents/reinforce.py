@@ -122,6 +122,9 @@ class REINFORCE(agent.AttributeSavingMixin, agent.Agent):
             assert torch.cuda.is_available()
             self.device = torch.device("cuda:{}".format(gpu))
             self.model.to(self.device)
+            from pfrl_amd.nn.mfma_linear import _fuse_small_mlps
+
+            _fuse_small_mlps(self.model)       # small tanh / ReLU MLPs: one launch each way
         else:
             self.device = torch.device("cpu")
         self.optimizer = optimizer

@@ -27,6 +27,7 @@ import torch.nn.functional as F
 from pfrl_amd import _native
 from pfrl_amd._native import check
 from pfrl_amd.nn import mfma_trunk as _t
+from pfrl_amd.nn.branched import Branched
 from pfrl_amd.nn.mfma_trunk import _ceil_div, _p, _stream
 
 _ENABLED = os.environ.get("PFRL_MFMA_LINEAR", "1") != "0"
@@ -390,32 +391,151 @@ class _LinearSlot(nn.Linear):
         return F.relu(y) if relu else y
 
 
+def _run_children(mods, x):
+    """The children ``mods`` one after the other, a ``_LinearSlot`` followed by a plain ``nn.ReLU``
+    as one node."""
+    i, n = 0, len(mods)
+    while i < n:
+        m = mods[i]
+        if (isinstance(m, _LinearSlot) and i + 1 < n and type(mods[i + 1]) is nn.ReLU
+                and torch.is_tensor(x) and supported(m, x)):
+            x = m(x, relu=True)
+            i += 2
+            continue
+        x = m(x)
+        i += 1
+    return x
+
+
 class _MlpSequential(nn.Sequential):
     """An ``nn.Sequential`` (same children, indices, state_dict) that runs a ``_LinearSlot``
     followed by a plain ``nn.ReLU`` as one node."""
 
     def forward(self, x):
+        return _run_children(list(self._modules.values()), x)
+
+
+# -------------------------------------------------------------------------------------------------
+# Whole small MLPs as one launch (ops.mlp_fused, csrc/mlp.hip): the 64-64 tanh policy and value
+# networks of the on-policy continuous-control agents, where every layer is one tile and a launch per
+# layer is all launch.
+# -------------------------------------------------------------------------------------------------
+_MLP_ACTS = {nn.Tanh: "tanh", nn.ReLU: "relu"}
+_MLP_LINEARS = (nn.Linear, _LinearSlot, _t._SmallLinearSlot)
+
+
+def _mlp_linear(m):
+    return type(m) in _MLP_LINEARS and m.bias is not None and m.weight.dtype == torch.float32
+
+
+def _find_mlp_run(mods):
+    """(start, end, activation) of the first maximal ``Linear, act, ..., Linear`` stretch of ``mods``
+    with at least one ``act`` (plain ``nn.Tanh`` / ``nn.ReLU``; ``Linear`` of the plain class or one of
+    its slots, float32, with bias) -- or None when there is no such stretch or that stretch is outside
+    what one launch covers: 2 or 3 layers, one kind of activation, widths up to 64, up to 512 inputs.
+    (A lone ``Linear`` is no MLP: it keeps the kernels it has.)"""
+    from pfrl_amd import ops
+
+    n = len(mods)
+    for s in range(n):
+        if not _mlp_linear(mods[s]):
+            continue
+        e = s
+        while e + 2 < n and type(mods[e + 1]) in _MLP_ACTS and _mlp_linear(mods[e + 2]):
+            e += 2
+        if e == s:
+            continue
+        lins = mods[s:e + 1:2]
+        if (len({type(m) for m in mods[s + 1:e:2]}) == 1 and len(lins) <= ops.MLP_MAX_LAYERS
+                and lins[0].in_features <= ops.MLP_MAX_IN
+                and all(m.out_features <= ops.MLP_MAX_WIDTH for m in lins)):
+            return s, e + 1, _MLP_ACTS[type(mods[s + 1])]
+        return None
+    return None
+
+
+def _mlp_route_open(seq):
+    """Differentiated calls take the route only where the container was made ``first_order``."""
+    return seq._mlp_first_order or not torch.is_grad_enabled()
+
+
+class _FusedMlpSequential(_MlpSequential):
+    """An ``nn.Sequential`` (same children, indices, state_dict; also the head-less views that
+    ``agents/_policy_split`` makes of one) whose ``Linear, act, ..., Linear`` stretch is ONE launch
+    where ``ops.mlp_fused_supported``; otherwise the children run as in ``_MlpSequential``."""
+
+    _mlp_first_order = True     # (instances carry their own; a copy made through the class starts here)
+
+    def forward(self, x):
+        from pfrl_amd import ops
+
         mods = list(self._modules.values())
-        i, n = 0, len(mods)
-        while i < n:
-            m = mods[i]
-            if (isinstance(m, _LinearSlot) and i + 1 < n and type(mods[i + 1]) is nn.ReLU
-                    and torch.is_tensor(x) and supported(m, x)):
-                x = m(x, relu=True)
-                i += 2
-                continue
-            x = m(x)
-            i += 1
-        return x
+        run = _find_mlp_run(mods) if _mlp_route_open(self) else None
+        if run is None:
+            return _run_children(mods, x)
+        s, e, act = run
+        x = _run_children(mods[:s], x)
+        layers = [(m.weight, m.bias) for m in mods[s:e:2]]
+        if not ops.mlp_fused_supported(x, layers, act):
+            return _run_children(mods[s:], x)
+        return _run_children(mods[e:], ops.mlp_fused(x, layers, act))
 
 
-def accelerate_mlp(model):
+class _FusedBranched(Branched):
+    """A ``Branched`` (same children) of two ``_FusedMlpSequential`` that begin with stretches of
+    equal depth: both stretches as ONE launch on the shared input, then what follows in each."""
+
+    def forward(self, *args, **kwargs):
+        from pfrl_amd import ops
+
+        kids = list(self.child_modules)
+        if (len(args) == 1 and not kwargs and len(kids) == 2
+                and all(type(k) is _FusedMlpSequential and _mlp_route_open(k) for k in kids)):
+            mods = [list(k._modules.values()) for k in kids]
+            runs = [_find_mlp_run(m) for m in mods]
+            if all(r is not None and r[0] == 0 for r in runs) and runs[0][1] == runs[1][1]:
+                layers = [[(m.weight, m.bias) for m in ms[:r[1]:2]] for ms, r in zip(mods, runs)]
+                acts = (runs[0][2], runs[1][2])
+                if ops.mlp_fused_supported(args[0], layers, acts):
+                    ys = ops.mlp_fused(args[0], layers, acts)
+                    return tuple(_run_children(ms[r[1]:], y) for ms, r, y in zip(mods, runs, ys))
+        return Branched.forward(self, *args, **kwargs)
+
+
+def _fuse_small_mlps(model, first_order=True):
+    """Only the whole-MLP route of :func:`accelerate_mlp`, for agents whose other layers keep the
+    kernels they have: every plain ``nn.Sequential`` inside ``model`` with a stretch that
+    ``_find_mlp_run`` accepts becomes a ``_FusedMlpSequential``, and a plain ``Branched`` of exactly two
+    of them that begin with stretches of equal depth a ``_FusedBranched``.  ``first_order=False``: the
+    route is taken under ``torch.no_grad()`` only (a model that is differentiated twice).  Returns
+    ``model`` (classes of containers change; children, parameters and state_dict keys do not)."""
+    from pfrl_amd import ops
+
+    if model is None or not ops.mlp_fused_enabled():
+        return model
+    for seq in [m for m in model.modules() if type(m) is nn.Sequential]:
+        if _find_mlp_run(list(seq._modules.values())) is not None:
+            seq.__class__ = _FusedMlpSequential
+            object.__setattr__(seq, "_mlp_first_order", bool(first_order))
+    for br in [m for m in model.modules() if type(m) is Branched]:
+        kids = list(br.child_modules)
+        if len(kids) == 2 and all(type(k) is _FusedMlpSequential for k in kids):
+            runs = [_find_mlp_run(list(k._modules.values())) for k in kids]
+            if runs[0][0] == 0 and runs[1][0] == 0 and runs[0][1] == runs[1][1]:
+                br.__class__ = _FusedBranched
+    return model
+
+
+def accelerate_mlp(model, first_order=True):
     """Route the ``nn.Linear`` layers of ``model`` (plain class, with bias, out_features >= 17)
     through the MFMA kernels and fuse ``Linear, ReLU`` neighbours of plain ``nn.Sequential``
-    containers; narrower layers get the narrow-head kernels (``accelerate_heads``).  Returns
+    containers; narrower layers get the narrow-head kernels (``accelerate_heads``).  Before that,
+    small MLPs (2 or 3 layers up to 64 wide, all ``nn.Tanh`` or all ``nn.ReLU``) become one launch
+    each way (``_fuse_small_mlps``; ``first_order=False``: only with gradients off).  Returns
     ``model`` (modified in place; parameters, names and state_dict keys unchanged)."""
     if model is None:
         return model
+    _fuse_small_mlps(model, first_order)
     for parent in list(model.modules()):
         for name, child in list(parent._modules.items()):
             if type(child) is nn.Linear and child.bias is not None and child.out_features >= MIN_OUT:

@@ -2041,6 +2041,160 @@ def gru_sequence(x, batch_sizes, h0, w_ih, w_hh, b_ih, b_hh):
 
 
 # ---------------------------------------------------------------------------------------------
+# whole small MLPs as one launch forward and one backward (csrc/mlp.hip)
+# ---------------------------------------------------------------------------------------------
+MLP_MAX_LAYERS = 3
+MLP_MAX_WIDTH = 64
+MLP_MAX_IN = 512
+MLP_MAX_ROWS = 65536
+MLP_ACTS = {"tanh": 0, "relu": 1}       # PFRL_MLP_TANH, PFRL_MLP_RELU
+# differentiated calls above this many input elements keep the library: measured (tools/mlp_time.py), forward + backward
+# at 16 384 x 376 takes 696 us here against 426 us; 2 048 x 376, the largest measured input that wins: 206 against 347
+MLP_MAX_TRAIN_INPUT = 2048 * 376
+
+
+def mlp_fused_enabled():
+    """``PFRL_MLP_FUSED=0`` turns the whole-MLP route off (read at every call: one process can compare
+    both routes)."""
+    return os.environ.get("PFRL_MLP_FUSED", "1") != "0"
+
+
+def _pad4(n):
+    return (n + 3) & ~3
+
+
+def _mlp_nets(layers, act):
+    """([[(w, b), ...] per network], [act per network]) of the two call forms of :func:`mlp_fused`."""
+    if isinstance(act, str):
+        return [list(layers)], [act]
+    return [list(net) for net in layers], list(act)
+
+
+class _MlpFused(torch.autograd.Function):
+    """meta = (acts, n_layers, small_m); params = w, b of every layer, network after network."""
+
+    @staticmethod
+    def forward(ctx, x, meta, *params):
+        acts, L, small_m = meta
+        nn_, (M, K0), dev = len(acts), x.shape, x.device
+        train = any(ctx.needs_input_grad)
+        V, I = ctypes.c_void_p, ctypes.c_int32
+        W, B, N = (V * (3 * nn_))(), (V * (3 * nn_))(), (I * (3 * nn_))()
+        S, Y, A = (V * (2 * nn_))(), (V * nn_)(), (I * nn_)(*acts)
+        ys, saves = [], []
+        for k in range(nn_):
+            for l in range(L):
+                w, b = params[2 * (k * L + l)], params[2 * (k * L + l) + 1]
+                W[3 * k + l], B[3 * k + l], N[3 * k + l] = w.data_ptr(), b.data_ptr(), w.shape[0]
+                if train and l + 1 < L:
+                    saves.append(torch.empty((M, w.shape[0]), dtype=torch.float32, device=dev))
+                    S[2 * k + l] = saves[-1].data_ptr()
+            ys.append(torch.empty((M, params[2 * (k * L + L - 1)].shape[0]), dtype=torch.float32, device=dev))
+            Y[k] = ys[-1].data_ptr()
+        check(_native.lib().pfrl_mlp_fwd(_ptr(x), M, K0, L, nn_, W, B, N, A, S, Y, small_m, _stream()), "mlp_fwd")
+        if train:
+            ctx.save_for_backward(x, *params, *saves)
+            ctx.meta = meta
+        return tuple(ys)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *dys):
+        acts, L, _ = ctx.meta
+        nn_ = len(acts)
+        x, params, saves = ctx.saved_tensors[0], ctx.saved_tensors[1:1 + 2 * nn_ * L], ctx.saved_tensors[1 + 2 * nn_ * L:]
+        (M, K0), dev, lib = x.shape, x.device, _native.lib()
+        V, I = ctypes.c_void_p, ctypes.c_int32
+        W, N, A = (V * (3 * nn_))(), (I * (3 * nn_))(), (I * nn_)(*acts)
+        S, DY, DX, G = (V * (2 * nn_))(), (V * nn_)(), (V * nn_)(), (V * nn_)()
+        slabs = lib.pfrl_mlp_bwd_slabs(M)
+        need_dx = ctx.needs_input_grad[0]
+        keep, sizes, dxs = [], [], []
+        for k in range(nn_):
+            floats = 0
+            for l in range(L):
+                w = params[2 * (k * L + l)]
+                W[3 * k + l], N[3 * k + l] = w.data_ptr(), w.shape[0]
+                floats += _pad4(w.numel()) + _pad4(w.shape[0])
+                if l + 1 < L:
+                    S[2 * k + l] = saves[k * (L - 1) + l].data_ptr()
+            sizes.append(floats)
+            dy = dys[k]
+            dy = torch.zeros((M, N[3 * k + L - 1]), dtype=torch.float32, device=dev) if dy is None else dy.contiguous()
+            keep.append(dy)
+            DY[k] = dy.data_ptr()
+            if need_dx:
+                dxs.append(torch.empty_like(x))
+                DX[k] = dxs[-1].data_ptr()
+        stride = max(sizes)
+        outs = [torch.empty(sizes[k], dtype=torch.float32, device=dev) for k in range(nn_)]
+        WS = (V * nn_)()
+        work = [torch.empty(slabs * stride, dtype=torch.float32, device=dev) for _ in range(nn_ if slabs > 1 else 0)]
+        for k in range(nn_):
+            G[k] = outs[k].data_ptr()
+            if slabs > 1:
+                WS[k] = work[k].data_ptr()
+        check(lib.pfrl_mlp_bwd(_ptr(x), M, K0, L, nn_, W, N, A, S, DY, DX if need_dx else None, G, WS, stride,
+                               _stream()), "mlp_bwd")
+        grads = []
+        for k in range(nn_):
+            off = 0
+            for l in range(L):
+                w, b = params[2 * (k * L + l)], params[2 * (k * L + l) + 1]
+                need_w, need_b = ctx.needs_input_grad[2 + 2 * (k * L + l):4 + 2 * (k * L + l)]
+                grads.append(outs[k][off:off + w.numel()].view_as(w) if need_w else None)
+                off += _pad4(w.numel())
+                grads.append(outs[k][off:off + b.numel()] if need_b else None)
+                off += _pad4(b.numel())
+        dx = None
+        if need_dx:
+            dx = dxs[0] if nn_ == 1 else dxs[0] + dxs[1]
+        return (dx, None) + tuple(grads)
+
+
+def mlp_fused_supported(x, layers, act):
+    """Inside the envelope of :func:`mlp_fused` (csrc/mlp.hip refuses the rest): one network, or two of
+    equal depth on the same ``x``; 1 to 3 ``(weight, bias)`` layers each, every width 1 .. 64 behind
+    1 .. 512 inputs, ``act`` "tanh" or "relu"; ``x`` [1 .. 65536, in_features]; everything float32,
+    contiguous and on ``x``'s CUDA device; a differentiated call of at most ``MLP_MAX_TRAIN_INPUT`` input
+    elements (above, the backward launch loses to the library).  ``PFRL_MLP_FUSED=0`` answers False."""
+    if not (mlp_fused_enabled() and torch.is_tensor(x) and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32
+            and x.is_contiguous() and 1 <= x.shape[0] <= MLP_MAX_ROWS and 1 <= x.shape[1] <= MLP_MAX_IN):
+        return False
+    nets, acts = _mlp_nets(layers, act)
+    if not (1 <= len(nets) <= 2 and len(acts) == len(nets) and all(a in MLP_ACTS for a in acts)
+            and 1 <= len(nets[0]) <= MLP_MAX_LAYERS and all(len(n) == len(nets[0]) for n in nets)):
+        return False
+    for net in nets:
+        fan_in = x.shape[1]
+        for w, b in net:
+            if b is None or not all(t.is_cuda and t.device == x.device and t.dtype == torch.float32
+                                    and t.is_contiguous() for t in (w, b)):
+                return False
+            if w.dim() != 2 or w.shape[1] != fan_in or not 1 <= w.shape[0] <= MLP_MAX_WIDTH or b.shape != w.shape[:1]:
+                return False
+            fan_in = w.shape[0]
+    if (x.numel() > MLP_MAX_TRAIN_INPUT and torch.is_grad_enabled()
+            and (x.requires_grad or any(t.requires_grad for net in nets for wb in net for t in wb))):
+        return False
+    return _native.available()
+
+
+def mlp_fused(x, layers, act, small_m=-1):
+    """``Linear, act, ..., Linear`` on ``x`` [M, in_features] as ONE HIP launch, and its backward as one
+    (two above 64 rows: the fold of the gradient slabs).  ``layers``: the ``(weight, bias)`` pairs of
+    one network with ``act`` "tanh" or "relu" -> y; or a pair of such lists with a pair of activations
+    (two networks of equal depth on the same ``x``, e.g. policy and value function) -> (y0, y1).  The
+    bits of a row of y depend on that row and the parameters only.  ``small_m``: up to this many rows
+    take the 16-row tile program (default: the launcher's).  Differentiable once."""
+    assert mlp_fused_supported(x, layers, act)
+    nets, acts = _mlp_nets(layers, act)
+    params = [t for net in nets for wb in net for t in wb]
+    out = _MlpFused.apply(x, (tuple(MLP_ACTS[a] for a in acts), len(nets[0]), int(small_m)), *params)
+    return out[0] if isinstance(act, str) else out
+
+
+# ---------------------------------------------------------------------------------------------
 # torch.randn on the device generator as ONE launch for several draws (csrc/philox.hip)
 # ---------------------------------------------------------------------------------------------
 _PHILOX_VARIANT = {}

@@ -1,0 +1,87 @@
+"""Time of a 64-64 MLP (the policy / value networks of the on-policy continuous-control agents), whole-MLP HIP route
+against the per-layer library path, in one process on the same inputs.
+
+The method of tools/gru_time.py: both variants are warmed up, they alternate window by window, a window is a number of calls
+between two device events sized from a trial to last at least --window-ms.  One JSON line per shape: mean, minimum and maximum
+of the windows in microseconds per call for both variants, and the largest difference of their results.
+
+    python tools/mlp_time.py                     # forward alone (no_grad) and forward + backward
+    python tools/mlp_time.py --pair              # policy and value function as a Branched (one launch for both)
+"""
+import argparse
+import copy
+import json
+import os
+import sys
+
+import torch
+from torch import nn
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import pfrl_amd  # noqa: E402,F401
+from pfrl_amd.nn import Branched, accelerate_mlp  # noqa: E402
+
+
+def make(obs, out, act, pair):
+    net = lambda o: nn.Sequential(nn.Linear(obs, 64), act(), nn.Linear(64, 64), act(), nn.Linear(64, o))  # noqa: E731
+    return Branched(net(out), net(1)) if pair else net(out)
+
+
+def call(model, x, backward):
+    if not backward:
+        with torch.no_grad():
+            return model(x)
+    y = model(x)
+    y = y if torch.is_tensor(y) else torch.cat(y, dim=1)
+    model.zero_grad()
+    y.sum().backward()
+    return y
+
+
+def window(fn, calls):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(calls):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / calls
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, nargs="+", default=[1, 64, 2048, 16384])
+    ap.add_argument("--obs", type=int, nargs="+", default=[11, 376])
+    ap.add_argument("--relu", action="store_true")
+    ap.add_argument("--pair", action="store_true")
+    ap.add_argument("--windows", type=int, default=10)
+    ap.add_argument("--window-ms", type=float, default=20.0)
+    args = ap.parse_args()
+    act = nn.ReLU if args.relu else nn.Tanh
+    for obs in args.obs:
+        torch.manual_seed(0)
+        base = make(obs, 6, act, args.pair).cuda()
+        off = copy.deepcopy(base)                   # (plain containers: the library's launches)
+        on = accelerate_mlp(copy.deepcopy(base))
+        for rows in args.rows:
+            x = torch.randn(rows, obs, device="cuda")
+            for backward in (False, True):
+                fns = {"route": lambda: call(on, x, backward), "library": lambda: call(off, x, backward)}
+                outs = {k: f() for k, f in fns.items()}
+                cat = lambda y: y if torch.is_tensor(y) else torch.cat(y, dim=1)     # noqa: E731
+                diff = float((cat(outs["route"]) - cat(outs["library"])).abs().max())
+                for f in fns.values():
+                    window(f, 20)
+                calls = {k: max(5, int(args.window_ms * 1e3 / window(f, 20))) for k, f in fns.items()}
+                times = {k: [] for k in fns}
+                for _ in range(args.windows):
+                    for k, f in fns.items():
+                        times[k].append(window(f, calls[k]))
+                rec = dict(obs=obs, rows=rows, pair=args.pair, backward=backward, max_abs_diff=diff)
+                for k, v in times.items():
+                    rec[k + "_us"] = dict(mean=sum(v) / len(v), min=min(v), max=max(v))
+                print(json.dumps(rec), flush=True)
+
+
+if __name__ == "__main__":
+    main()
