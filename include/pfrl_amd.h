@@ -1197,6 +1197,35 @@ int pfrl_mlp_bwd(const float *x, int32_t M, int32_t in_features, int32_t n_layer
                  const float *const *saved, const float *const *dy, float *const *dx, float *const *grads,
                  float *const *slab_ws, int64_t slab_stride, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Whole wide MLPs as one launch (csrc/mlp_wide.hip): the 256-256 and 400-300 ReLU policy and twin-critic
+ * networks of the replay actor-critic agents: the q_func1 / q_func2 / policy evaluations of
+ * update_q_func, update_policy_and_temperature and _batch_act_train (pfrl/agents/soft_actor_critic.py:
+ * 214, 273, 343), of update_q_func, update_policy and _batch_act_train (pfrl/agents/td3.py:181, 233,
+ * 281) and of pfrl/agents/ddpg.py:265; the networks of examples/mujoco/reproduction/soft_actor_critic/
+ * train_soft_actor_critic.py:172-199.  Activations stay in LDS, weights stream.
+ * f32 in, f32 accumulate.
+ * Envelope: n_layers 2 or 3 Linear layers with bias, act (PFRL_MLP_TANH or PFRL_MLP_RELU) behind every
+ * layer but the last; input [M][K1 + K2] given as x1 [M][K1] and an optional x2 [M][K2] (K2 == 0: x2
+ * is ignored), rows of any alignment, 1 <= K1 + K2 <= 1024; hidden widths 1 .. 512, last width 1 .. 64
+ * (widths[l], the same for both networks); 1 <= M <= 65536; n_nets 1 or 2.  w / b[3 k + l] as in
+ * pfrl_mlp_fwd; save / saved[2 k + l] is hidden layer l's output after the activation ([M][width];
+ * the halves of a [2][M][width] tensor serve); y[k] / dy[k] are [M][last width].
+ * pfrl_mlp_wide_fwd: save may be NULL, and so may its entries.  The bits of an output row depend on
+ *   that row and the parameters only: not on M, the row's position or n_nets.
+ * pfrl_mlp_wide_dx: the frozen-parameter backward: d_l = (d_{l+1} W_{l+1}) act'(a_l) from dy down to
+ *   layer 0, then dx [M][ncol] = sum over the networks (network 0 first) of d_0 W_0[:, col0 : col0 +
+ *   ncol], K = K1 + K2 being W_0's row length; 1 <= ncol <= 64, col0 + ncol <= K.  No weight
+ *   gradients, no atomics, one order of every sum.
+ * Outside the envelope, null or misaligned pointers: PFRL_ERR_ARG, nothing is written.  n_nets == 0 is
+ * the empty launch: 0, nothing is written. */
+int pfrl_mlp_wide_fwd(const float *x1, const float *x2, int32_t M, int32_t K1, int32_t K2, int32_t n_layers,
+                      int32_t n_nets, const float *const *w, const float *const *b, const int32_t *widths,
+                      int32_t act, float *const *save, float *const *y, void *stream);
+int pfrl_mlp_wide_dx(int32_t M, int32_t K, int32_t n_layers, int32_t n_nets, const float *const *w,
+                     const int32_t *widths, int32_t act, const float *const *saved, const float *const *dy,
+                     float *dx, int32_t col0, int32_t ncol, void *stream);
+
 /* Ragged gather of sampled episodes for recurrent updates: batch_recurrent_experiences
  * (pfrl/replay_buffer.py:219-287) over EpisodicReplayBuffer.sample_episodes (pfrl/replay_buffers/
  * episodic.py:48-85, windows cut by random_subseq).  An episode is a run of consecutive

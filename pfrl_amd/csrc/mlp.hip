@@ -36,7 +36,7 @@
 // More: at most kMaxSlabs slabs in a workspace, added in slab order in f64 by k_mlp_fold behind the same
 // entry point (the f32 adds of pfrl_splitk_reduce missed the accuracy rule of the tests for bias
 // gradients).  No atomics; one order of every sum.
-#include "recurrent_mfma.h"
+#include "mlp_common.h"
 
 namespace {
 
@@ -70,28 +70,6 @@ struct BwdNet {
 struct BwdArgs {
     BwdNet net[2];
 };
-
-// `rows` x 64 floats of a row-major matrix with `ld` columns, from (r0, c0) on, into dst; zeros beyond
-// row nr - 1 and column nc - 1.  Consecutive threads take consecutive columns.
-__device__ __forceinline__ void stage(Tile *dst, const float *__restrict__ src, int rows, int r0, int nr, int c0,
-                                      int nc, int ld, int tid) {
-    for (int idx = tid; idx < rows * 64; idx += kThreads) {
-        const int r = idx >> 6, c = idx & 63;
-        const int gr = r0 + r, gc = c0 + c;
-        float v = 0.f;
-        if (gr < nr && gc < nc) v = src[(size_t)gr * ld + gc];
-        dst[r][c] = v;
-    }
-}
-
-__device__ __forceinline__ float activate(float v, int act) {
-    return act == PFRL_MLP_TANH ? tanhf(v) : (v < 0.f ? 0.f : v);
-}
-
-// d times act'(a), from the activation's output
-__device__ __forceinline__ float act_grad(float d, float a, int act) {
-    return act == PFRL_MLP_TANH ? d * (1.f - a * a) : (a > 0.f ? d : 0.f);
-}
 
 // acc[j] += A[arow + c16][0 .. kpad) . W[16 ct(j) + c16][0 .. kpad): NT column tiles against one row tile
 template <int RT>
@@ -154,7 +132,7 @@ __global__ __launch_bounds__(kThreads) PFRL_NO_PACKED_FP32 void k_mlp_fwd(const 
     f32x4 acc[NT];
 
     // the second layer's weights travel while the first layer multiplies
-    if (L > 1) stage(sW[1], net.w[1], 16 * ((net.n[1] + 15) >> 4), 0, net.n[1], 0, net.n[0], net.n[0], tid);
+    if (L > 1) stage<kThreads>(sW[1], net.w[1], 16 * ((net.n[1] + 15) >> 4), 0, net.n[1], 0, net.n[0], net.n[0], tid);
 
     // layer 0: x and W_0 in chunks of 64 k
     {
@@ -163,8 +141,8 @@ __global__ __launch_bounds__(kThreads) PFRL_NO_PACKED_FP32 void k_mlp_fwd(const 
         for (int j = 0; j < NT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int c0 = 0; c0 < K0; c0 += kChunk) {
             __syncthreads();                                  // (the previous chunk has been read)
-            stage(sA, x, RT, row0, M, c0, K0, K0, tid);
-            stage(sW[0], net.w[0], 16 * nt, 0, N, c0, K0, K0, tid);
+            stage<kThreads>(sA, x, RT, row0, M, c0, K0, K0, tid);
+            stage<kThreads>(sW[0], net.w[0], 16 * nt, 0, N, c0, K0, K0, tid);
             __syncthreads();
             fwd_mma<RT>(acc, sA, sW[0], (min(kChunk, K0 - c0) + 15) & ~15, nt, wave, c16, kq);
         }
@@ -172,7 +150,7 @@ __global__ __launch_bounds__(kThreads) PFRL_NO_PACKED_FP32 void k_mlp_fwd(const 
         fwd_epilogue<RT>(acc, sA, net.b[0], L == 1 ? net.y : net.save[0], L == 1, act, N, nt, row0, M, wave, c16, kq);
     }
     if (L == 1) return;
-    if (L > 2) stage(sW[0], net.w[2], 16 * ((net.n[2] + 15) >> 4), 0, net.n[2], 0, net.n[1], net.n[1], tid);
+    if (L > 2) stage<kThreads>(sW[0], net.w[2], 16 * ((net.n[2] + 15) >> 4), 0, net.n[2], 0, net.n[1], net.n[1], tid);
     __syncthreads();
     {
         const int N = net.n[1], nt = (N + 15) >> 4;
@@ -283,9 +261,9 @@ __global__ __launch_bounds__(kThreads) PFRL_NO_PACKED_FP32 void k_mlp_bwd(const 
             if (l >= L) continue;
             const int N = net.n[l], K = net.n[l - 1], ntn = (N + 15) >> 4, ntk = (K + 15) >> 4;
             __syncthreads();                                  // (sD is written, sA and sW have been read)
-            if (l == L - 1) stage(sD, net.dy, kBwdRows, row0, M, 0, N, N, tid);
-            stage(sA, net.a[l - 1], kBwdRows, row0, M, 0, K, K, tid);
-            stage(sW, net.w[l], 16 * ntn, 0, N, 0, K, K, tid);
+            if (l == L - 1) stage<kThreads>(sD, net.dy, kBwdRows, row0, M, 0, N, N, tid);
+            stage<kThreads>(sA, net.a[l - 1], kBwdRows, row0, M, 0, K, K, tid);
+            stage<kThreads>(sW, net.w[l], 16 * ntn, 0, N, 0, K, K, tid);
             __syncthreads();
             if (wave < ntn) bwd_wgrad(gw[l - 1], &gb[l], sD, sA, ntk, wave, c16, kq);
             f32x4 d[4];
@@ -310,9 +288,9 @@ __global__ __launch_bounds__(kThreads) PFRL_NO_PACKED_FP32 void k_mlp_bwd(const 
             if (c >= nch) continue;
             const int c0 = c * kChunk, ntk = min(4, (K0 - c0 + 15) >> 4);
             __syncthreads();
-            if (c == 0 && L == 1) stage(sD, net.dy, kBwdRows, row0, M, 0, N, N, tid);
-            stage(sA, x, kBwdRows, row0, M, c0, K0, K0, tid);
-            if (net.dx != nullptr) stage(sW, net.w[0], 16 * ntn, 0, N, c0, K0, K0, tid);
+            if (c == 0 && L == 1) stage<kThreads>(sD, net.dy, kBwdRows, row0, M, 0, N, N, tid);
+            stage<kThreads>(sA, x, kBwdRows, row0, M, c0, K0, K0, tid);
+            if (net.dx != nullptr) stage<kThreads>(sW, net.w[0], 16 * ntn, 0, N, c0, K0, K0, tid);
             __syncthreads();
             if (wave < ntn) bwd_wgrad(gw0[c], c == 0 ? &gb[0] : nullptr, sD, sA, ntk, wave, c16, kq);
             if (net.dx != nullptr) {
@@ -375,8 +353,6 @@ __global__ __launch_bounds__(kThreads) void k_mlp_fold(FoldArgs a, int slabs, lo
     for (int g = 0; g < slabs; ++g) s += (double)p[(size_t)g * stride];
     a.out[k][e] = (float)s;
 }
-
-inline bool aligned4(const void *p) { return ((uintptr_t)p & 3) == 0; }
 
 // the envelope both entry points share
 const char *check_envelope(const float *x, int32_t M, int32_t K0, int32_t L, int32_t n_nets, const float *const *w,

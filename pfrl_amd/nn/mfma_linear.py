@@ -412,7 +412,19 @@ class _MlpSequential(nn.Sequential):
     followed by a plain ``nn.ReLU`` as one node."""
 
     def forward(self, x):
-        return _run_children(list(self._modules.values()), x)
+        from pfrl_amd import ops
+
+        mods = list(self._modules.values())
+        # gradients off (acting, target networks): a wide Linear, act, ..., Linear stretch as ONE launch
+        run = _find_mlp_run(mods, wide=True) if not torch.is_grad_enabled() and ops.mlp_wide_enabled() else None
+        if run is None:
+            return _run_children(mods, x)
+        s, e, act = run
+        x = _run_children(mods[:s], x)
+        layers = [(m.weight, m.bias) for m in mods[s:e:2]]
+        if not (torch.is_tensor(x) and ops.mlp_wide_supported((x,), [layers], act)):
+            return _run_children(mods[s:], x)
+        return _run_children(mods[e:], ops.mlp_wide_fwd((x,), [layers], act)[0])
 
 
 # -------------------------------------------------------------------------------------------------
@@ -428,12 +440,14 @@ def _mlp_linear(m):
     return type(m) in _MLP_LINEARS and m.bias is not None and m.weight.dtype == torch.float32
 
 
-def _find_mlp_run(mods):
+def _find_mlp_run(mods, wide=False):
     """(start, end, activation) of the first maximal ``Linear, act, ..., Linear`` stretch of ``mods``
     with at least one ``act`` (plain ``nn.Tanh`` / ``nn.ReLU``; ``Linear`` of the plain class or one of
     its slots, float32, with bias) -- or None when there is no such stretch or that stretch is outside
-    what one launch covers: 2 or 3 layers, one kind of activation, widths up to 64, up to 512 inputs.
-    (A lone ``Linear`` is no MLP: it keeps the kernels it has.)"""
+    what one launch covers: 2 or 3 layers, one kind of activation, widths up to 64, up to 512 inputs
+    (``ops.mlp_fused``); with ``wide``, instead: a hidden width above 64, none above 512, last width up to
+    64, up to 1024 inputs (``ops.mlp_wide_fwd``).  (A lone ``Linear`` is no MLP: it keeps the kernels it
+    has.)"""
     from pfrl_amd import ops
 
     n = len(mods)
@@ -446,11 +460,15 @@ def _find_mlp_run(mods):
         if e == s:
             continue
         lins = mods[s:e + 1:2]
-        if (len({type(m) for m in mods[s + 1:e:2]}) == 1 and len(lins) <= ops.MLP_MAX_LAYERS
-                and lins[0].in_features <= ops.MLP_MAX_IN
-                and all(m.out_features <= ops.MLP_MAX_WIDTH for m in lins)):
-            return s, e + 1, _MLP_ACTS[type(mods[s + 1])]
-        return None
+        if len({type(m) for m in mods[s + 1:e:2]}) != 1 or len(lins) > ops.MLP_MAX_LAYERS:
+            return None
+        widths = [m.out_features for m in lins]
+        if wide:
+            inside = (lins[0].in_features <= ops.MLP_WIDE_MAX_IN and widths[-1] <= ops.MLP_WIDE_MAX_LAST
+                      and ops.MLP_MAX_WIDTH < max(widths[:-1]) <= ops.MLP_WIDE_MAX_HIDDEN)
+        else:
+            inside = lins[0].in_features <= ops.MLP_MAX_IN and max(widths) <= ops.MLP_MAX_WIDTH
+        return (s, e + 1, _MLP_ACTS[type(mods[s + 1])]) if inside else None
     return None
 
 

@@ -88,6 +88,8 @@ def twin_plan(q1, q2, inputs):
 class _TwinQ(torch.autograd.Function):
     @staticmethod
     def forward(ctx, obs, action, *params):
+        from pfrl_amd import ops
+
         w1a, b1a, w2a, b2a, w3a, b3a, w1b, b1b, w2b, b2b, w3b, b3b = params
         lib = _native.lib()
         dev = obs.device
@@ -98,6 +100,14 @@ class _TwinQ(torch.autograd.Function):
         h2 = torch.empty((2, M, H2), dtype=torch.float32, device=dev)
         q = torch.empty((2, M, No), dtype=torch.float32, device=dev)
         st = _stream()
+        nets = [[(w1a, b1a), (w2a, b2a), (w3a, b3a)], [(w1b, b1b), (w2b, b2b), (w3b, b3b)]]
+        ctx.wide = min(H1, H2) > ops.MLP_MAX_WIDTH and ops.mlp_wide_supported((obs, action), nets, "relu")
+        if ctx.wide:
+            # the whole of both networks as one launch (csrc/mlp_wide.hip), h1 / h2 saved for either backward
+            ops.mlp_wide_fwd((obs, action), nets, "relu", [[h1[0], h2[0]], [h1[1], h2[1]]], [q[0], q[1]])
+            ctx.save_for_backward(obs, action, h1, h2, w1a, w2a, w3a, w1b, w2b, w3b)
+            ctx.ptrs = [[t.data_ptr() for t in (w1a, b1a, w2a, b2a)], [t.data_ptr() for t in (w1b, b1b, w2b, b2b)]]
+            return q[0], q[1]
         # layer 1 reads its input rows from obs and action directly (no cat)
         check(lib.pfrl_linear_fwd_twin(_pair(obs, obs), _pair(action, action), Ko, _pair(w1a, w1b),
                                        _pair(b1a, b1b), _pair(h1[0], h1[1]), M, K, H1, 1, st),
@@ -112,6 +122,8 @@ class _TwinQ(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, ga, gb):
+        from pfrl_amd import ops
+
         obs, action, h1, h2, w1a, w2a, w3a, w1b, w2b, w3b = ctx.saved_tensors
         lib = _native.lib()
         dev = obs.device
@@ -130,6 +142,11 @@ class _TwinQ(torch.autograd.Function):
         dh2 = torch.empty((2, M, H2), **f32)
         dh1 = torch.empty((2, M, H1), **f32)
         grads = [None] * 12
+        if ctx.wide and not need_w and need_da and K - Ko <= ops.MLP_WIDE_MAX_LAST:
+            # frozen critics (the policy loss): the whole chain down to the action columns as one launch
+            nets = [[(w1a, None), (w2a, None), (w3a, None)], [(w1b, None), (w2b, None), (w3b, None)]]
+            da = ops.mlp_wide_dx(nets, "relu", [[h1[0], h2[0]], [h1[1], h2[1]]], [ga, gb], Ko, K - Ko)
+            return (None, da) + tuple(grads)
         if need_w:
             dw3 = torch.empty((2,) + tuple(w3a.shape), **f32)
             db3 = torch.empty((2, No), **f32)

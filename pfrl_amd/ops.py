@@ -2195,6 +2195,109 @@ def mlp_fused(x, layers, act, small_m=-1):
 
 
 # ---------------------------------------------------------------------------------------------
+# whole wide MLPs as one launch: forward, and the frozen-parameter input gradient (csrc/mlp_wide.hip)
+# ---------------------------------------------------------------------------------------------
+MLP_WIDE_MAX_HIDDEN = 512
+MLP_WIDE_MAX_LAST = 64
+MLP_WIDE_MAX_IN = 1024
+# rows the route admits: nn/twin_mlp.MAX_BATCH, the largest shape timed (tools/mlp_time.py --wide)
+MLP_WIDE_MAX_ROWS = 512
+
+
+def mlp_wide_enabled():
+    """``PFRL_MLP_WIDE=1`` opens the wide whole-MLP route, ``0`` (and, today, leaving it unset) keeps the
+    per-layer launches; read at every call, so one process can compare both routes.  Off unless asked
+    for because every shape timed so far loses to the chain it replaces (tools/mlp_time.py --wide,
+    captured graphs, us per pass, route / per-layer: twin 393-256-256-1 forward 52.4 / 18.1 at 256 rows
+    and 53.0 / 25.4 at 512, with the frozen backward 87.5 / 37.7 and 88.1 / 45.7; single 376-256-256-34
+    forward 23.0 / 18.3 at 64 rows and 23.1 / 15.9 at 256; 376-400-300-17 38.6 / 23.9 and 39.0 / 26.1):
+    a 16-row tile per workgroup leaves the whole network to 16 compute units at 256 rows."""
+    return os.environ.get("PFRL_MLP_WIDE", "0") == "1"
+
+
+def mlp_wide_supported(xs, nets, act):
+    """Inside what the wide whole-MLP route admits (csrc/mlp_wide.hip refuses what is outside its
+    envelope): ``xs`` one or two column blocks [M, K1], [M, K2] of the input, 1 <= M <= 512 and
+    K1 + K2 <= 1024; ``nets`` one or two lists of 2 or 3 ``(weight, bias)`` layers of equal shapes, a
+    hidden width above 64 (narrower networks are ``mlp_fused``'s) and none above 512, last width up to
+    64; ``act`` "tanh" or "relu"; everything float32, contiguous, on one CUDA device.
+    Without ``PFRL_MLP_WIDE=1`` the answer is False (``mlp_wide_enabled``)."""
+    if not (mlp_wide_enabled() and 1 <= len(xs) <= 2 and 1 <= len(nets) <= 2 and act in MLP_ACTS):
+        return False
+    x = xs[0]
+    if not all(torch.is_tensor(t) and t.is_cuda and t.device == x.device and t.dim() == 2 and t.dtype == torch.float32
+               and t.is_contiguous() and t.shape[0] == x.shape[0] and t.shape[1] >= 1 for t in xs):
+        return False
+    fan_in = sum(t.shape[1] for t in xs)
+    if not (1 <= x.shape[0] <= MLP_WIDE_MAX_ROWS and fan_in <= MLP_WIDE_MAX_IN and 2 <= len(nets[0]) <= 3):
+        return False
+    widths = [w.shape[0] for w, _ in nets[0]]
+    if not (all(1 <= n <= MLP_WIDE_MAX_HIDDEN for n in widths[:-1]) and max(widths[:-1]) > MLP_MAX_WIDTH
+            and 1 <= widths[-1] <= MLP_WIDE_MAX_LAST):
+        return False
+    for net in nets:
+        if len(net) != len(widths):
+            return False
+        k = fan_in
+        for (w, b), n in zip(net, widths):
+            if b is None or not all(t.is_cuda and t.device == x.device and t.dtype == torch.float32
+                                    and t.is_contiguous() for t in (w, b)):
+                return False
+            if tuple(w.shape) != (n, k) or tuple(b.shape) != (n,):
+                return False
+            k = n
+    return _native.available()
+
+
+def _wide_tables(nets):
+    V, I = ctypes.c_void_p, ctypes.c_int32
+    W, B = (V * (3 * len(nets)))(), (V * (3 * len(nets)))()
+    for k, net in enumerate(nets):
+        for l, (w, b) in enumerate(net):
+            W[3 * k + l], B[3 * k + l] = w.data_ptr(), b.data_ptr() if b is not None else None
+    return W, B, (I * 3)(*[w.shape[0] for w, _ in nets[0]])
+
+
+def mlp_wide_fwd(xs, nets, act, saves=None, ys=None):
+    """``Linear, act, ..., Linear`` of one or two networks on the input ``cat(xs, 1)`` as ONE HIP launch
+    (no autograd node: the callers are under ``no_grad`` or own the node).  ``saves[k][l]``, when
+    given, receives hidden layer l's activations of network k ([M, width]); ``ys[k]`` the output
+    (allocated when None).  Returns the list of outputs."""
+    assert mlp_wide_supported(xs, nets, act)
+    V = ctypes.c_void_p
+    M, L, nn_ = xs[0].shape[0], len(nets[0]), len(nets)
+    W, B, N = _wide_tables(nets)
+    if ys is None:
+        ys = [torch.empty((M, N[L - 1]), dtype=torch.float32, device=xs[0].device) for _ in nets]
+    S, Y = (V * (2 * nn_))(), (V * nn_)(*[y.data_ptr() for y in ys])
+    for k in range(nn_ if saves is not None else 0):
+        for l in range(L - 1):
+            S[2 * k + l] = saves[k][l].data_ptr()
+    x2 = xs[1] if len(xs) == 2 else None
+    check(_native.lib().pfrl_mlp_wide_fwd(_ptr(xs[0]), _ptr(x2) if x2 is not None else None, M, xs[0].shape[1],
+                                          x2.shape[1] if x2 is not None else 0, L, nn_, W, B, N, MLP_ACTS[act], S, Y,
+                                          _stream()), "mlp_wide_fwd")
+    return ys
+
+
+def mlp_wide_dx(nets, act, saves, dys, col0, ncol):
+    """The gradient of ``sum_k <dys[k], net_k(x)>`` with respect to the input columns ``col0 : col0 +
+    ncol`` (ncol <= 64) as ONE HIP launch, the parameters taken as constants: ``saves[k][l]`` are the
+    hidden activations :func:`mlp_wide_fwd` saved, ``dys[k]`` [M, last width] contiguous."""
+    V = ctypes.c_void_p
+    M, L, nn_ = dys[0].shape[0], len(nets[0]), len(nets)
+    W, _, N = _wide_tables(nets)
+    S, DY = (V * (2 * nn_))(), (V * nn_)(*[d.data_ptr() for d in dys])
+    for k in range(nn_):
+        for l in range(L - 1):
+            S[2 * k + l] = saves[k][l].data_ptr()
+    dx = torch.empty((M, ncol), dtype=torch.float32, device=dys[0].device)
+    check(_native.lib().pfrl_mlp_wide_dx(M, nets[0][0][0].shape[1], L, nn_, W, N, MLP_ACTS[act], S, DY, _ptr(dx),
+                                         col0, ncol, _stream()), "mlp_wide_dx")
+    return dx
+
+
+# ---------------------------------------------------------------------------------------------
 # torch.randn on the device generator as ONE launch for several draws (csrc/philox.hip)
 # ---------------------------------------------------------------------------------------------
 _PHILOX_VARIANT = {}

@@ -7,6 +7,8 @@ of the windows in microseconds per call for both variants, and the largest diffe
 
     python tools/mlp_time.py                     # forward alone (no_grad) and forward + backward
     python tools/mlp_time.py --pair              # policy and value function as a Branched (one launch for both)
+    python tools/mlp_time.py --wide              # the wide route (csrc/mlp_wide.hip) against the per-layer launches,
+                                                 # PFRL_MLP_WIDE=1 against 0, each as replays of a captured graph
 """
 import argparse
 import copy
@@ -48,6 +50,79 @@ def window(fn, calls):
     return e0.elapsed_time(e1) * 1e3 / calls
 
 
+def wide_cases():
+    """(name, rows, fn): fn() runs the pass once; the route is chosen by PFRL_MLP_WIDE when fn is called."""
+    from pfrl_amd.nn import ConcatObsAndAction
+    from pfrl_amd.nn.twin_mlp import twin_forward
+
+    def mlp(i, h1, h2, o, concat=False):
+        head = [ConcatObsAndAction()] if concat else []
+        return accelerate_mlp(nn.Sequential(*head, nn.Linear(i, h1), nn.ReLU(), nn.Linear(h1, h2), nn.ReLU(),
+                                            nn.Linear(h2, o)).cuda())
+
+    def single(net, x):
+        def fn():
+            with torch.no_grad():
+                return net(x)
+        return fn
+
+    def twin(q1, q2, obs, action, frozen):
+        for p in list(q1.parameters()) + list(q2.parameters()):
+            p.requires_grad_(False)
+        a = action.clone().requires_grad_(frozen)
+
+        def fn():
+            if not frozen:
+                with torch.no_grad():
+                    return torch.cat(twin_forward(q1, q2, (obs, a)), 1)
+            ya, yb = twin_forward(q1, q2, (obs, a))
+            return torch.autograd.grad((ya + yb).sum(), a)[0]
+        return fn
+
+    torch.manual_seed(0)
+    cases = []
+    for rows in (256, 512):
+        obs, action = torch.randn(rows, 376, device="cuda"), torch.randn(rows, 17, device="cuda")
+        q1, q2 = mlp(393, 256, 256, 1, True), mlp(393, 256, 256, 1, True)
+        cases += [("twin 393-256-256-1 forward", rows, twin(q1, q2, obs, action, False)),
+                  ("twin 393-256-256-1 forward + frozen backward", rows, twin(q1, q2, obs, action, True))]
+    for rows in (64, 256):
+        x = torch.randn(rows, 376, device="cuda")
+        cases += [("single 376-256-256-34 forward", rows, single(mlp(376, 256, 256, 34), x)),
+                  ("single 376-400-300-17 forward", rows, single(mlp(376, 400, 300, 17), x))]
+    return cases
+
+
+def wide_main(args):
+    """Route on against route off, each captured once (20 calls a graph) and timed as alternating windows of replays."""
+    from pfrl_amd.agents import _capture
+
+    class Holder:
+        pool = None
+
+    for name, rows, fn in wide_cases():
+        graphs, outs = {}, {}
+        for k, env in (("route", "1"), ("per_layer", "0")):
+            os.environ["PFRL_MLP_WIDE"] = env
+            outs[k] = fn().clone()
+            _capture.warm_up("cuda", lambda i: fn())
+            graphs[k] = _capture.capture(Holder, lambda: [fn() for _ in range(20)])[0]
+        os.environ.pop("PFRL_MLP_WIDE")
+        diff = float((outs["route"] - outs["per_layer"]).abs().max())
+        fns = {k: g.replay for k, g in graphs.items()}
+        for f in fns.values():
+            window(f, 20)
+        calls = {k: max(5, int(args.window_ms * 1e3 / (20 * window(f, 20)))) for k, f in fns.items()}
+        times = {k: [] for k in fns}
+        for _ in range(args.windows):
+            for k, f in fns.items():
+                times[k].append(window(f, calls[k]) / 20)
+        rec = dict(case=name, rows=rows, max_abs_diff=diff)
+        for k, v in times.items():
+            rec[k + "_us"] = dict(mean=sum(v) / len(v), min=min(v), max=max(v))
+        print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, nargs="+", default=[1, 64, 2048, 16384])
@@ -56,7 +131,10 @@ def main():
     ap.add_argument("--pair", action="store_true")
     ap.add_argument("--windows", type=int, default=10)
     ap.add_argument("--window-ms", type=float, default=20.0)
+    ap.add_argument("--wide", action="store_true")
     args = ap.parse_args()
+    if args.wide:
+        return wide_main(args)
     act = nn.ReLU if args.relu else nn.Tanh
     for obs in args.obs:
         torch.manual_seed(0)
