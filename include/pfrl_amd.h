@@ -404,8 +404,8 @@ int pfrl_ppo_minibatch_f32act(int64_t M, const int64_t *idx, const float *adv, c
                               void *stream);
 
 /* ------------------------------------------------------------------------
- * TRPO's policy update around the Fisher-vector product (pfrl/agents/trpo.py; the product itself
- * stays autograd's double backward).  csrc/trpo.hip.  Every sum is an f64 sum in a fixed order: two
+ * TRPO's policy update around the Fisher-vector product (pfrl/agents/trpo.py; the product itself is
+ * autograd's double backward, or pfrl_mlp_jvp + pfrl_mlp_bwd + pfrl_trpo_fvp_finish).  csrc/trpo.hip.  Every sum is an f64 sum in a fixed order: two
  * calls on the same operands give the same bits.
  * ------------------------------------------------------------------------ */
 /* TRPO._compute_gain (trpo.py:415-420) and mean KL(old || new) (trpo.py:560-562, :666-670:
@@ -443,6 +443,18 @@ int pfrl_trpo_scale_step(const float *d, const float *Fd, double max_kl, float *
  * bit.  step_size == 0 copies base (the restore of trpo.py:694-699). */
 int pfrl_params_axpy(int32_t n_tensors, float *const *params, const int64_t *numel, const float *base,
                      const float *full_step, float step_size, void *stream);
+/* The last launch of a fused Fisher-vector product (the `_hessian_vector_product` of pfrl/agents/trpo.py
+ * plus `+ damping * vec`, trpo.py:557-598, for a Gaussian policy on a small MLP: pfrl_mlp_jvp, then
+ * pfrl_mlp_bwd, then this).  packed [packed_n]: pfrl_mlp_bwd's gradient, segments padded to 4 floats; the
+ * flat vectors v and out [n] follow list(policy.parameters()) without padding.  Segment t (at most
+ * PFRL_FVP_MAX_SEGS) copies packed[seg_src[t] .. + seg_len[t]) to out[seg_dst[t] ..); the P <= 32 scale
+ * parameters at p_off get Hpp [P][P] times v[p_off .. p_off + P) (f64 sum, rounded once; P == 0, Hpp NULL:
+ * a fixed covariance); then out += damping * v, a multiply and an add, each rounded.  Segments and scale
+ * parameters must tile [0, n) and stay inside packed: otherwise PFRL_ERR_ARG, nothing is written. */
+#define PFRL_FVP_MAX_SEGS 6
+int pfrl_trpo_fvp_finish(const float *packed, int64_t packed_n, int32_t n_segs, const int64_t *seg_src,
+                         const int64_t *seg_dst, const int64_t *seg_len, const float *Hpp, int32_t P,
+                         int64_t p_off, const float *v, float damping, int64_t n, float *out, void *stream);
 
 /* REINFORCE (pfrl/agents/reinforce.py:176-195) on the M stored steps of a batch of episodes: per row
  *   row = fl(fl(-ret) log pi(a | s)) - fl(beta H),   out2 = {sum(row) * inv_batchsize, mean H},
@@ -1196,6 +1208,18 @@ int pfrl_mlp_bwd(const float *x, int32_t M, int32_t in_features, int32_t n_layer
                  const float *const *w, const int32_t *widths, const int32_t *act,
                  const float *const *saved, const float *const *dy, float *const *dx, float *const *grads,
                  float *const *slab_ws, int64_t slab_stride, void *stream);
+/* The forward-mode tangent of ONE such network with respect to its parameters, the J v half of the
+ * Gauss-Newton form J^T diag(col_scale) J of the Fisher-vector product (`_hessian_vector_product` of
+ * pfrl/agents/trpo.py, called from trpo.py:557-598; J^T is pfrl_mlp_bwd).  Same envelope.  saved[l]: the
+ * hidden activations pfrl_mlp_fwd wrote through save (not recomputed).  vw[l] / vb[l]: the direction,
+ * shaped like w[l] / the bias; 4-byte alignment suffices (they point into an unpadded flat vector).
+ *   t_z = W_l t_{l-1} + V_l a_{l-1} + c_l (t_{-1} = 0, a_{-1} = x),  t_l = act'(a_l) t_z,
+ *   ty [M][last width] = t_z of the last layer, times col_scale[column] when col_scale is not NULL.
+ * One launch, no atomics; small_m as pfrl_mlp_fwd.  The bits of a row of ty depend on that row, the
+ * parameters and the direction only.  Refusals as above: PFRL_ERR_ARG, nothing is written. */
+int pfrl_mlp_jvp(const float *x, int32_t M, int32_t in_features, int32_t n_layers, const float *const *w,
+                 const int32_t *widths, int32_t act, const float *const *saved, const float *const *vw,
+                 const float *const *vb, const float *col_scale, float *ty, int32_t small_m, void *stream);
 
 /* ------------------------------------------------------------------------
  * Whole wide MLPs as one launch (csrc/mlp_wide.hip): the 256-256 and 400-300 ReLU policy and twin-critic

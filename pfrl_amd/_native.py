@@ -190,6 +190,7 @@ EXPORTS = {
     "pfrl_cg_init": (ctypes.c_int, "ppppppqp"),
     "pfrl_cg_step": (ctypes.c_int, "ppppppqfp"),
     "pfrl_trpo_scale_step": (ctypes.c_int, "ppdpppqp"),
+    "pfrl_trpo_fvp_finish": (ctypes.c_int, "pqippppiqpfqpp"),
     "pfrl_params_axpy": (ctypes.c_int, "ippppfp"),
     "pfrl_reinforce_loss": (ctypes.c_int, "pppiiffpppp"),
     "pfrl_reinforce_gaussian_loss": (ctypes.c_int, "ppppiiffppppp"),
@@ -266,6 +267,7 @@ EXPORTS = {
     "pfrl_mlp_fwd": (ctypes.c_int, "piiiippppppip"),
     "pfrl_mlp_bwd_slabs": (ctypes.c_int, "i"),
     "pfrl_mlp_bwd": (ctypes.c_int, "piiiippppppppqp"),
+    "pfrl_mlp_jvp": (ctypes.c_int, "piiippipppppip"),
     "pfrl_mlp_wide_fwd": (ctypes.c_int, "ppiiiiipppippp"),
     "pfrl_mlp_wide_dx": (ctypes.c_int, "iiiippipppiip"),
     "pfrl_philox_normal": (ctypes.c_int, "QQipppppip"),

@@ -15,7 +15,10 @@ host reads the reference ends every small step with:
   gain / KL / entropy   pfrl_trpo_gaussian_eval behind the head-less policy (``_policy_split``), once
                         with the gradient of the gain and once per line-search trial; any other
                         policy keeps the torch.distributions expressions
-  Fisher-vector product the reference's double backward through autograd, unchanged
+  Fisher-vector product ``fused_fisher``, a Gaussian policy that is one small MLP: pfrl_mlp_jvp,
+                        pfrl_mlp_bwd and pfrl_trpo_fvp_finish per product (``ops.gaussian_mlp_fisher``:
+                        the Gauss-Newton form the Hessian of the KL takes at old = new); otherwise
+                        the reference's double backward through autograd, unchanged
   conjugate gradient    pfrl_cg_init / pfrl_cg_step: ``conjugate_gradient_max_iter`` unconditional
                         steps, the scalars and the convergence flag in a device state block
   KL-scaled step        pfrl_trpo_scale_step
@@ -24,8 +27,8 @@ host reads the reference ends every small step with:
   value function        minibatch positions from PPO's walk of the ``random`` stream, one captured
                         graph per minibatch step
 
-Out of scope: recurrent TRPO on the device rollout, a fused Fisher-vector product, the CG loop as
-one captured graph.
+Out of scope: recurrent TRPO on the device rollout, a fused Fisher-vector product for softmax or
+wider policies, the CG loop as one captured graph.
 """
 import collections
 import contextlib
@@ -165,7 +168,9 @@ class TRPO(PPO):
     a line search, the value function by ``vf_optimizer``.
 
     ``fused_gaussian_eval`` / ``device_cg`` / ``fused_param_step`` / ``capture_vf_step`` (device
-    route only): False keeps the corresponding part of the update as eager torch on the device."""
+    route only): False keeps the corresponding part of the update as eager torch on the device.
+    ``fused_fisher`` (device route, behind ``fused_gaussian_eval``): the Fisher-vector product as
+    launches where ``ops.gaussian_mlp_fisher_supported``; False keeps autograd's double backward."""
 
     saved_attributes = ("policy", "vf", "vf_optimizer", "obs_normalizer")
 
@@ -177,7 +182,8 @@ class TRPO(PPO):
                  act_deterministically=False, max_grad_norm=None, value_stats_window=1000,
                  entropy_stats_window=1000, kl_stats_window=100, policy_step_size_stats_window=100,
                  logger=getLogger(__name__), fused_gaussian_eval=True, device_cg=True,
-                 fused_param_step=True, capture_vf_step=True, value_pass_chunk=16384):
+                 fused_param_step=True, capture_vf_step=True, fused_fisher=True,
+                 value_pass_chunk=16384):
         from pfrl_amd.nn import Branched, RecurrentBranched
 
         self.policy = policy
@@ -223,6 +229,7 @@ class TRPO(PPO):
         self.device_cg = bool(device_cg)
         self.fused_param_step = bool(fused_param_step)
         self.capture_vf_step = bool(capture_vf_step)
+        self.fused_fisher = bool(fused_fisher)
 
         self.kl_record = collections.deque(maxlen=kl_stats_window)
         self.policy_step_size_record = collections.deque(maxlen=policy_step_size_stats_window)
@@ -289,17 +296,12 @@ class TRPO(PPO):
 
         self._line_search(params, full_step, trial)
 
-    def _kl_constrained_step(self, params, kl, flat_gain_grads):
+    def _kl_constrained_step(self, params, kl, flat_gain_grads, fisher_vector_product=None):
         """Reference :557-598: the step direction F^-1 g by conjugate gradient around Fisher-vector
-        products (a double backward through ``kl``), scaled to the KL bound."""
-        flat_kl_grads = _flat_grads([kl], params, create_graph=True)
-        assert flat_kl_grads.requires_grad
-        damping = self.conjugate_gradient_damping
-
-        def fisher_vector_product(vec):
-            vec = torch.as_tensor(vec)
-            return _hessian_vector_product(flat_kl_grads, params, vec) + damping * vec
-
+        products, scaled to the KL bound.  The product is a double backward through ``kl``, or a
+        ready ``fisher_vector_product`` (damping included; ``kl`` is not used then)."""
+        if fisher_vector_product is None:
+            fisher_vector_product = self._fisher_by_double_backward(params, kl)
         on_dev = self._host is None
         if on_dev and self.device_cg:
             direction = ops.conjugate_gradient_device(fisher_vector_product, flat_gain_grads,
@@ -310,6 +312,17 @@ class TRPO(PPO):
                                        max_iter=self.conjugate_gradient_max_iter)
         dId = float(direction.dot(fisher_vector_product(direction)))
         return (2.0 * self.max_kl / (dId + 1e-8)) ** 0.5 * direction
+
+    def _fisher_by_double_backward(self, params, kl):
+        flat_kl_grads = _flat_grads([kl], params, create_graph=True)
+        assert flat_kl_grads.requires_grad
+        damping = self.conjugate_gradient_damping
+
+        def fisher_vector_product(vec):
+            vec = torch.as_tensor(vec)
+            return _hessian_vector_product(flat_kl_grads, params, vec) + damping * vec
+
+        return fisher_vector_product
 
     def _line_search(self, params, full_step, trial):
         """Reference :600-699.  ``trial()`` evaluates the policy as it stands and returns (gain,
@@ -374,8 +387,9 @@ class TRPO(PPO):
     def _policy_step_fused(self, found, states, actions, advs, log_prob_old):
         """The same step with the Gaussian row arithmetic in pfrl_trpo_gaussian_eval: once with the
         gradient of the gain (backpropagated through the head-less policy by autograd), once per
-        line-search trial without.  The KL whose double backward is the Fisher-vector product is
-        the reference's expression on the head's own distribution."""
+        line-search trial without.  The Fisher-vector product is ``ops.gaussian_mlp_fisher``
+        (``fused_fisher``), or the double backward of the reference's KL expression on the head's own
+        distribution."""
         body, head, scale_of = found.view.child_modules[0], found.head, found.scale
         params = list(self.policy.parameters())
         mean = body(states)
@@ -387,10 +401,14 @@ class TRPO(PPO):
             flat_gain_grads = _flat_grads([mean, scale], params, grad_outputs=[dmean, dscale])
         else:       # (a constant scale)
             flat_gain_grads = _flat_grads([mean], params, grad_outputs=[dmean])
-        with torch.no_grad():
-            distrib_old = head(mean_old)
-        kl = torch.mean(torch.distributions.kl_divergence(distrib_old, head(mean)))
-        full_step = self._kl_constrained_step(params, kl, flat_gain_grads.detach())
+        if self.fused_fisher and ops.gaussian_mlp_fisher_supported(self.policy, states):
+            fvp = ops.gaussian_mlp_fisher(self.policy, states, self.conjugate_gradient_damping)
+            full_step = self._kl_constrained_step(params, None, flat_gain_grads.detach(), fvp)
+        else:
+            with torch.no_grad():
+                distrib_old = head(mean_old)
+            kl = torch.mean(torch.distributions.kl_divergence(distrib_old, head(mean)))
+            full_step = self._kl_constrained_step(params, kl, flat_gain_grads.detach())
 
         def trial():
             with torch.no_grad(), evaluating(self.policy):

@@ -36,6 +36,22 @@
 // More: at most kMaxSlabs slabs in a workspace, added in slab order in f64 by k_mlp_fold behind the same
 // entry point (the f32 adds of pfrl_splitk_reduce missed the accuracy rule of the tests for bias
 // gradients).  No atomics; one order of every sum.
+//
+// Tangent pass (k_mlp_jvp: J v of the last layer's output with respect to the parameters, the forward-mode
+// half of a Gauss-Newton / Fisher-vector product whose other half, J^T, is the backward above).  With the
+// direction V_l, c_l shaped like W_l, b_l and the hidden activations a_l that the forward saved:
+//   t_z = W_l t_{l-1} + V_l a_{l-1} + c_l  (t_{-1} = 0, a_{-1} = x),   t_l = act'(a_l) t_z,   ty = t_z of the last
+// layer, times an optional per-column factor.  The forward's tile programs: layer 0 is V_0 x + c_0 with x and
+// V_0 streamed in 64-k chunks (V_0 in W_0's place, no W_0 product); a hidden layer has W_l, V_l, the a_{l-1}
+// tile and the t_{l-1} tile in LDS and runs both products as ONE accumulator chain, W t first, then V a, over
+// ascending k blocks: a row of ty has the same bits at any M, any position and in either program.  The
+// direction is read with scalar bounds-checked loads (`stage`): its pointers are 4-byte aligned only, they
+// point into a flat vector whose segments are not padded.  LDS, under the 64 KB that a static allocation
+// may take:
+//   16-row program: a and t tiles 2 x 4 352 B + THREE weight buffers 3 x 17 408 B = 60 928 B.  W_1 and V_1
+//                   travel while layer 0 multiplies, W_2 while layer 1 does, V_2 as soon as W_1 has been read.
+//   64-row program: a and t tiles 2 x 17 408 B + ONE weight buffer = 52 224 B (W, V and both tiles at once
+//                   would be 69 632 B): W_l and V_l pass through the one buffer in turn, the chain unchanged.
 #include "mlp_common.h"
 
 namespace {
@@ -60,6 +76,12 @@ struct FwdNet {
 };
 struct FwdArgs {
     FwdNet net[2];
+};
+
+struct JvpArgs {
+    const float *w[3], *a[2], *vw[3], *vb[3], *col_scale;
+    float *ty;
+    int n[3], act;
 };
 
 struct BwdNet {
@@ -168,6 +190,107 @@ __global__ __launch_bounds__(kThreads) PFRL_NO_PACKED_FP32 void k_mlp_fwd(const 
         for (int j = 0; j < NT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         fwd_mma<RT>(acc, sA, sW[0], ((net.n[1] + 15) >> 4) << 4, nt, wave, c16, kq);
         fwd_epilogue<RT>(acc, sA, net.b[2], net.y, true, act, N, nt, row0, M, wave, c16, kq);
+    }
+}
+
+// The tangent of a layer from its accumulators: t_z = acc + c; a hidden layer's t = act'(a) t_z goes into sT
+// (a: the layer's saved output, staged in sA; columns beyond N as zeros), the last layer's t_z, times the
+// column factor, to global memory.
+template <int RT>
+__device__ __forceinline__ void jvp_epilogue(const f32x4 (&acc)[RT / 16], const Tile *sA, Tile *sT,
+                                             const float *__restrict__ vb, const float *__restrict__ col_scale,
+                                             float *__restrict__ ty, bool last, int act, int N, int ntiles, int row0,
+                                             int M, int wave, int c16, int kq) {
+    constexpr int NT = RT / 16;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int ct = RT == 64 ? j : wave;
+        if (ct >= ntiles) continue;
+        const int col = 16 * ct + c16;
+        const float cv = col < N ? vb[col] : 0.f;
+        const float cs = last && col_scale != nullptr && col < N ? col_scale[col] : 1.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = (RT == 64 ? 16 * wave : 0) + 4 * kq + i;
+            const float v = acc[j][i] + cv;
+            if (!last)
+                sT[r][col] = col < N ? act_grad(v, sA[r][col], act) : 0.f;
+            else if (col < N && row0 + r < M)
+                ty[(size_t)(row0 + r) * N + col] = col_scale != nullptr ? v * cs : v;
+        }
+    }
+}
+
+// a whole [N][K] matrix (weights or direction), rows padded to the tile
+__device__ __forceinline__ void stage_mat(Tile *dst, const float *__restrict__ src, int N, int K, int tid) {
+    stage<kThreads>(dst, src, 16 * ((N + 15) >> 4), 0, N, 0, K, K, tid);
+}
+
+template <int RT>
+__global__ __launch_bounds__(kThreads) PFRL_NO_PACKED_FP32 void k_mlp_jvp(const float *__restrict__ x, JvpArgs g, int M,
+                                                                         int K0, int L) {
+    constexpr int NB = RT == 16 ? 3 : 1, NT = RT / 16;
+    __shared__ __attribute__((aligned(16))) float sA[RT][kLd];
+    __shared__ __attribute__((aligned(16))) float sT[RT][kLd];
+    __shared__ __attribute__((aligned(16))) float sW[NB][kMaxW][kLd];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c16 = lane & 15, kq = lane >> 4;
+    const int row0 = blockIdx.x * RT;
+    const int act = g.act;
+    f32x4 acc[NT];
+
+    if constexpr (NB == 3) {
+        if (L > 1) {
+            stage_mat(sW[1], g.w[1], g.n[1], g.n[0], tid);
+            stage_mat(sW[2], g.vw[1], g.n[1], g.n[0], tid);
+        }
+    }
+    // layer 0: V_0 x in chunks of 64 k
+    {
+        const int N = g.n[0], nt = (N + 15) >> 4;
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int c0 = 0; c0 < K0; c0 += kChunk) {
+            __syncthreads();                                  // (the previous chunk has been read)
+            stage<kThreads>(sA, x, RT, row0, M, c0, K0, K0, tid);
+            stage<kThreads>(sW[0], g.vw[0], 16 * nt, 0, N, c0, K0, K0, tid);
+            __syncthreads();
+            fwd_mma<RT>(acc, sA, sW[0], (min(kChunk, K0 - c0) + 15) & ~15, nt, wave, c16, kq);
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < 3; ++l) {
+        if (l >= L) continue;
+        const int N = g.n[l], nt = (N + 15) >> 4;
+        const bool last = l == L - 1;
+        if (l > 0) {
+            // (behind the previous epilogue's barrier: sA = a_{l-1}, sT = t_{l-1}, every buffer read)
+            const int kpad = ((g.n[l - 1] + 15) >> 4) << 4;
+#pragma unroll
+            for (int j = 0; j < NT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (NB == 3) {
+                if (l == 1 && L > 2) stage_mat(sW[0], g.w[2], g.n[2], g.n[1], tid);
+                fwd_mma<RT>(acc, sT, l == 1 ? sW[1] : sW[0], kpad, nt, wave, c16, kq);
+                fwd_mma<RT>(acc, sA, l == 1 ? sW[2] : sW[1], kpad, nt, wave, c16, kq);
+            } else {
+                stage_mat(sW[0], g.w[l], N, g.n[l - 1], tid);
+                __syncthreads();
+                fwd_mma<RT>(acc, sT, sW[0], kpad, nt, wave, c16, kq);
+                __syncthreads();
+                stage_mat(sW[0], g.vw[l], N, g.n[l - 1], tid);
+                __syncthreads();
+                fwd_mma<RT>(acc, sA, sW[0], kpad, nt, wave, c16, kq);
+            }
+        }
+        if (!last) {
+            __syncthreads();                                  // (both tiles and this layer's matrices have been read)
+            stage<kThreads>(sA, g.a[l], RT, row0, M, 0, N, N, tid);
+            if constexpr (NB == 3) {
+                if (l == 1) stage_mat(sW[1], g.vw[2], g.n[2], g.n[1], tid);
+            }
+            __syncthreads();
+        }
+        jvp_epilogue<RT>(acc, sA, sT, g.vb[l], g.col_scale, g.ty, last, act, N, nt, row0, M, wave, c16, kq);
+        if (!last) __syncthreads();
     }
 }
 
@@ -407,6 +530,41 @@ extern "C" int pfrl_mlp_fwd(const float *x, int32_t M, int32_t in_features, int3
     else
         hipLaunchKernelGGL(k_mlp_fwd<64>, dim3((M + 63) / 64, n_nets), dim3(kThreads), 0, (hipStream_t)stream, x, a,
                            (int)M, (int)in_features, (int)n_layers);
+    PFRL_LAUNCH_CHECK();
+}
+
+extern "C" int pfrl_mlp_jvp(const float *x, int32_t M, int32_t in_features, int32_t n_layers, const float *const *w,
+                            const int32_t *widths, int32_t act, const float *const *saved, const float *const *vw,
+                            const float *const *vb, const float *col_scale, float *ty, int32_t small_m,
+                            void *stream) {
+    const char *err = check_envelope(x, M, in_features, n_layers, 1, w, widths, &act);
+    PFRL_CHECK_ARG(err == nullptr, err);
+    PFRL_CHECK_ARG(vw != nullptr && vb != nullptr && ty != nullptr && (n_layers == 1 || saved != nullptr),
+                   "pfrl_mlp_jvp: null pointer");
+    PFRL_CHECK_ARG(aligned4(ty) && aligned4(col_scale), "pfrl_mlp_jvp: misaligned pointer");
+    JvpArgs g{};
+    for (int l = 0; l < n_layers; ++l) {
+        g.w[l] = w[l];
+        g.vw[l] = vw[l];
+        g.vb[l] = vb[l];
+        g.n[l] = widths[l];
+        PFRL_CHECK_ARG(g.vw[l] != nullptr && g.vb[l] != nullptr && aligned4(g.vw[l]) && aligned4(g.vb[l]),
+                       "pfrl_mlp_jvp: null or misaligned direction");
+    }
+    for (int l = 0; l + 1 < n_layers; ++l) {
+        g.a[l] = saved[l];
+        PFRL_CHECK_ARG(g.a[l] != nullptr && aligned4(g.a[l]), "pfrl_mlp_jvp: null or misaligned activations");
+    }
+    g.col_scale = col_scale;
+    g.ty = ty;
+    g.act = act;
+    const int lim = small_m < 0 ? kSmallM : small_m;
+    if (M <= lim)
+        hipLaunchKernelGGL(k_mlp_jvp<16>, dim3((M + 15) / 16), dim3(kThreads), 0, (hipStream_t)stream, x, g, (int)M,
+                           (int)in_features, (int)n_layers);
+    else
+        hipLaunchKernelGGL(k_mlp_jvp<64>, dim3((M + 63) / 64), dim3(kThreads), 0, (hipStream_t)stream, x, g, (int)M,
+                           (int)in_features, (int)n_layers);
     PFRL_LAUNCH_CHECK();
 }
 

@@ -1,6 +1,7 @@
 // TRPO's policy update around the Fisher-vector product (pfrl/agents/trpo.py:415-699,
-// pfrl/utils/conjugate_gradient.py).  The product itself stays autograd's double backward; what
-// surrounds it in the reference is a chain of small launches that each end in a host read
+// pfrl/utils/conjugate_gradient.py).  The product itself is autograd's double backward, or for a Gaussian
+// policy on a small MLP pfrl_mlp_jvp + pfrl_mlp_bwd (mlp.hip) + pfrl_trpo_fvp_finish; what surrounds it
+// in the reference is a chain of small launches that each end in a host read
 // (`if torch.norm(residual) < tol`, `float(new_gain)`, `float(new_kl)`).  Here:
 //   pfrl_trpo_gaussian_eval   gain, KL(old || new), entropy of a state-independent-scale Gaussian
 //                             policy over the whole dataset (+ the gradient of the gain), one launch
@@ -8,6 +9,8 @@
 //   pfrl_cg_init / _step      conjugate gradient with every scalar in a device state block
 //   pfrl_trpo_scale_step      full_step = sqrt(2 max_kl / (d.Fd + 1e-8)) d
 //   pfrl_params_axpy          param_i = base + step_size * full_step over all parameter tensors
+//   pfrl_trpo_fvp_finish      the packed gradient of pfrl_mlp_bwd into the flat product, the scale
+//                             parameters' block H_pp v_p, and the damping
 // All sums are f64 in a fixed order (wave shuffles, LDS in wave order, partials in block order):
 // two runs give the same bits.  No float atomics.
 #include <hip/hip_runtime.h>
@@ -321,6 +324,33 @@ __global__ __launch_bounds__(kThreads) void k_params_axpy(AxpyArgs a, const floa
     }
 }
 
+// The flat Fisher-vector product from its parts: body element i of segment s is packed[src_s + i - dst_s]
+// (pfrl_mlp_bwd's packed layout against the unpadded flat vector), the P scale parameters at p_off get
+// (H_pp v_p)[p] in f64, and both damping * v on top: a multiply and an add, each rounded, as
+// `Hv + damping * vec` of trpo.py:583-586.
+struct FvpSegs {
+    int64_t src[PFRL_FVP_MAX_SEGS], dst[PFRL_FVP_MAX_SEGS], len[PFRL_FVP_MAX_SEGS];
+    int32_t n;
+};
+
+__global__ __launch_bounds__(kThreads) void k_trpo_fvp_finish(const float *__restrict__ packed, FvpSegs segs,
+                                                              const float *__restrict__ Hpp, int P, int64_t p_off,
+                                                              const float *__restrict__ v, float damping,
+                                                              int64_t n, float *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    float h = 0.f;
+    if (i >= p_off && i < p_off + P) {
+        double s = 0.0;
+        for (int q = 0; q < P; ++q) s += (double)Hpp[(i - p_off) * P + q] * (double)v[p_off + q];
+        h = (float)s;
+    } else {
+        for (int t = 0; t < segs.n; ++t)
+            if (i >= segs.dst[t] && i < segs.dst[t] + segs.len[t]) h = packed[segs.src[t] + (i - segs.dst[t])];
+    }
+    out[i] = __fadd_rn(h, __fmul_rn(damping, v[i]));
+}
+
 inline int chunks_of(int64_t n) { return (int)((n + kChunk - 1) / kChunk); }
 
 }  // namespace
@@ -416,5 +446,33 @@ extern "C" int pfrl_params_axpy(int32_t n_tensors, float *const *params, const i
     if (chunks == 0) return 0;
     hipLaunchKernelGGL(k_params_axpy, dim3(chunks), dim3(kThreads), 0, (hipStream_t)stream, a, base,
                        full_step, step_size);
+    PFRL_LAUNCH_CHECK();
+}
+
+extern "C" int pfrl_trpo_fvp_finish(const float *packed, int64_t packed_n, int32_t n_segs, const int64_t *seg_src,
+                                    const int64_t *seg_dst, const int64_t *seg_len, const float *Hpp, int32_t P,
+                                    int64_t p_off, const float *v, float damping, int64_t n, float *out,
+                                    void *stream) {
+    PFRL_CHECK_ARG(n >= 1 && n_segs >= 1 && n_segs <= PFRL_FVP_MAX_SEGS && P >= 0 && P <= kMaxA,
+                   "pfrl_trpo_fvp_finish: n >= 1, 1 <= segments <= 6, 0 <= P <= 32");
+    PFRL_CHECK_ARG(packed && seg_src && seg_dst && seg_len && v && out && (P == 0 || Hpp),
+                   "pfrl_trpo_fvp_finish: null pointer");
+    FvpSegs segs{};
+    int64_t covered = P;
+    for (int t = 0; t < n_segs; ++t) {
+        PFRL_CHECK_ARG(seg_src[t] >= 0 && seg_len[t] >= 1 && seg_src[t] + seg_len[t] <= packed_n &&
+                           seg_dst[t] >= 0 && seg_dst[t] + seg_len[t] <= n &&
+                           (seg_dst[t] + seg_len[t] <= p_off || seg_dst[t] >= p_off + P),
+                       "pfrl_trpo_fvp_finish: a segment outside the packed or the flat vector, or over the scale parameters");
+        segs.src[t] = seg_src[t];
+        segs.dst[t] = seg_dst[t];
+        segs.len[t] = seg_len[t];
+        covered += seg_len[t];
+    }
+    PFRL_CHECK_ARG(p_off >= 0 && p_off + P <= n && covered == n,
+                   "pfrl_trpo_fvp_finish: segments and scale parameters do not cover the flat vector");
+    segs.n = n_segs;
+    hipLaunchKernelGGL(k_trpo_fvp_finish, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       (hipStream_t)stream, packed, segs, Hpp, (int)P, p_off, v, damping, n, out);
     PFRL_LAUNCH_CHECK();
 }

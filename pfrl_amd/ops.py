@@ -2195,6 +2195,171 @@ def mlp_fused(x, layers, act, small_m=-1):
 
 
 # ---------------------------------------------------------------------------------------------
+# the Fisher-vector product of a Gaussian policy on such an MLP as launches (csrc/mlp.hip: pfrl_mlp_jvp,
+# pfrl_mlp_bwd; csrc/trpo.hip: pfrl_trpo_fvp_finish)
+# ---------------------------------------------------------------------------------------------
+# products above this many input elements keep autograd's double backward: measured (tools/mlp_time.py --fvp, us per
+# product, this route against the double backward) 2 048 x 11: 63 against 1 132; 5 000 x 376, the largest input measured:
+# 257 against 1 120.  Nothing larger has been timed, so nothing larger is taken.
+FISHER_MAX_INPUT = 5000 * 376
+
+
+def _void_ptrs(values, n=None):
+    """A ``void *[n]`` of addresses (None or missing: NULL)."""
+    arr = (ctypes.c_void_p * (len(values) if n is None else n))()
+    for i, v in enumerate(values):
+        arr[i] = v
+    return arr
+
+
+def mlp_jvp(x, weights, act, saved, vw, vb, col_scale=None, small_m=-1, out=None):
+    """``(J v) * col_scale`` [M, last width]: the forward-mode tangent of ``Linear, act, ..., Linear`` on
+    ``x`` [M, in_features] with respect to its parameters, along the direction ``vw[l]`` / ``vb[l]`` (shaped
+    like the weights and biases; float32 tensors of any 4-byte alignment, e.g. views into a flat vector),
+    as ONE launch (pfrl_mlp_jvp).  ``weights``: the ``weight`` tensors; ``saved``: the hidden activations
+    ``pfrl_mlp_fwd`` wrote through ``save``; ``act`` "tanh" or "relu"."""
+    M, K0 = x.shape
+    L = len(weights)
+    assert 1 <= L <= MLP_MAX_LAYERS and len(vw) == L and len(vb) == L and len(saved) == L - 1
+    fan_in = K0
+    for w, dw, db in zip(weights, vw, vb):
+        assert w.shape[1] == fan_in and dw.numel() == w.numel() and db.numel() == w.shape[0]
+        assert all(t.dtype == torch.float32 and t.device == x.device for t in (w, dw, db))
+        fan_in = w.shape[0]
+    assert all(tuple(a.shape) == (M, w.shape[0]) for a, w in zip(saved, weights))
+    if out is None:
+        out = torch.empty((M, fan_in), dtype=torch.float32, device=x.device)
+    N = (ctypes.c_int32 * 3)(*[w.shape[0] for w in weights])
+    check(_native.lib().pfrl_mlp_jvp(
+        _ptr(x), M, K0, L, _void_ptrs([_ptr(w).value for w in weights], 3), N, MLP_ACTS[act],
+        _void_ptrs([_ptr(a).value for a in saved], 2), _void_ptrs([_ptr(t).value for t in vw], 3),
+        _void_ptrs([_ptr(t).value for t in vb], 3), _ptr(col_scale), _ptr(out), int(small_m), _stream()), "mlp_jvp")
+    return out
+
+
+def _gaussian_mlp_parts(policy, x):
+    """(split, [(weight, bias)], act, scale parameter or None) when ``gaussian_mlp_fisher`` serves
+    ``policy`` on ``x``, else None."""
+    from pfrl_amd.agents import _policy_split
+    from pfrl_amd.nn.mfma_linear import _find_mlp_run
+
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous()
+            and 1 <= x.shape[0] <= MLP_MAX_ROWS and x.numel() <= FISHER_MAX_INPUT and _native.available()):
+        return None
+    split = _policy_split.gaussian_policy(policy, x.device)
+    if split is None:
+        return None
+    mods = list(split.view._modules.values())
+    run = _find_mlp_run(mods)
+    if run is None or (run[0], run[1]) != (0, len(mods)) or mods[0].in_features != x.shape[1]:
+        return None
+    layers = [(m.weight, m.bias) for m in mods[::2]]
+    body = [t for wb in layers for t in wb]
+    rest = [p for p in policy.parameters() if not any(p is t for t in body)]
+    var = None if split.fixed is not None else split.head.var_param
+    if len(rest) != (0 if var is None else 1) or (var is not None and rest[0] is not var):
+        return None
+    everything = body + rest
+    if not all(t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device for t in everything):
+        return None
+    if len(list(policy.parameters())) != len(everything) or (var is not None and var.numel() > GAUSSIAN_MAX_A):
+        return None
+    return split, layers, run[2], var
+
+
+def gaussian_mlp_fisher_supported(policy, x):
+    """Whether :func:`gaussian_mlp_fisher` serves ``policy`` on ``x``: the policy is ``Sequential(Linear,
+    act, ..., Linear, head)`` whose head-less part is one ``ops.mlp_fused`` stretch (2 or 3 layers up to 64
+    wide, up to 512 inputs, all tanh or all ReLU) and whose head is a Gaussian with a state-independent
+    or fixed scale; every parameter is a body parameter or the head's scale parameter; everything float32,
+    contiguous and on ``x``'s CUDA device; ``x`` [1 .. 65 536, in_features] of at most ``FISHER_MAX_INPUT``
+    elements."""
+    return _gaussian_mlp_parts(policy, x) is not None
+
+
+def gaussian_mlp_fisher(policy, x, damping=0.0, small_m=-1):
+    """``fvp(vec) -> F vec + damping * vec`` for the Fisher matrix F of ``policy`` on the states ``x``, i.e.
+    the Hessian of ``mean(kl_divergence(old, policy(x)))`` at old = new (reference pfrl/agents/trpo.py:
+    557-598 around ``_hessian_vector_product``), over ``list(policy.parameters())`` flattened.  At old = new
+    that Hessian is the Gauss-Newton form ``J^T diag(1 / (M s^2)) J`` on the body (J: the Jacobian of the
+    mean) plus ``Js^T diag(2 / s^2) Js`` on the scale parameters (Js = d scale / d p), no cross block.
+
+    Prepared here, once: a no-grad ``pfrl_mlp_fwd`` that saves the hidden activations, the column factor,
+    ``H_pp`` (autograd through the head's own scale expression), the workspaces and the segment table.
+    Each ``fvp`` call is launches only -- pfrl_mlp_jvp, pfrl_mlp_bwd (+ its fold above 64 rows),
+    pfrl_trpo_fvp_finish -- without autograd or allocation: it returns the SAME tensor every time,
+    overwritten by the next call."""
+    parts = _gaussian_mlp_parts(policy, x)
+    assert parts is not None, "outside gaussian_mlp_fisher_supported"
+    split, layers, act, var = parts
+    lib, dev, (M, K0), L = _native.lib(), x.device, x.shape, len(layers)
+    V, I, Q = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+    weights = [w.detach() for w, _ in layers]
+    widths = [w.shape[0] for w in weights]
+    A = widths[-1]
+    f32 = dict(dtype=torch.float32, device=dev)
+    saved = [torch.empty((M, n), **f32) for n in widths[:-1]]
+    ty = torch.empty((M, A), **f32)
+    W, B, N = _void_ptrs([w.data_ptr() for w in weights], 3), _void_ptrs([b.data_ptr() for _, b in layers], 3), \
+        (I * 3)(*widths)
+    S, acts = _void_ptrs([a.data_ptr() for a in saved], 2), (I * 1)(MLP_ACTS[act])
+    with torch.no_grad():
+        check(lib.pfrl_mlp_fwd(_ptr(x), M, K0, L, 1, W, B, N, acts, S, _void_ptrs([ty.data_ptr()]), int(small_m),
+                               _stream()), "mlp_fwd")
+        s = split.scale().detach().to(torch.float32)
+        col_scale = (1.0 / (M * s * s)).contiguous()
+    P, Hpp = 0, None
+    if var is not None:
+        with torch.enable_grad():
+            sc = split.scale()
+            Js = torch.stack([torch.autograd.grad(sc[j], var, retain_graph=True)[0].reshape(-1) for j in range(A)])
+        P = var.numel()
+        # (the products in float64, rounded once: entries reach 2 A / s^2)
+        Js, s64 = Js.double(), s.double()
+        Hpp = (Js.t() @ ((2.0 / (s64 * s64))[:, None] * Js)).float().contiguous()
+    # the packed gradient's segments against the flat vector of list(policy.parameters())
+    offs, off = {}, 0
+    for p in policy.parameters():
+        offs[id(p)] = off
+        off += p.numel()
+    n = off
+    src, dst, length, packed_n = [], [], [], 0
+    for w, b in layers:
+        for t in (w, b):
+            src.append(packed_n)
+            dst.append(offs[id(t)])
+            length.append(t.numel())
+            packed_n += _pad4(t.numel())
+    nseg = len(src)
+    SRC, DST, LEN = (Q * nseg)(*src), (Q * nseg)(*dst), (Q * nseg)(*length)
+    p_off = offs[id(var)] if var is not None else n
+    slabs = lib.pfrl_mlp_bwd_slabs(M)
+    packed = torch.empty(packed_n, **f32)
+    work = torch.empty(slabs * packed_n, **f32) if slabs > 1 else None
+    out = torch.empty(n, **f32)
+    G, WS, DY = _void_ptrs([packed.data_ptr()]), _void_ptrs([None if work is None else work.data_ptr()]), \
+        _void_ptrs([ty.data_ptr()])
+    damping = float(damping)
+
+    def fvp(vec):
+        vec = torch.as_tensor(vec)
+        assert vec.is_cuda and vec.dtype == torch.float32 and vec.numel() == n and vec.is_contiguous()
+        base = vec.data_ptr()
+        VW = _void_ptrs([base + 4 * d for d in dst[0::2]], 3)
+        VB = _void_ptrs([base + 4 * d for d in dst[1::2]], 3)
+        stream = _stream()
+        check(lib.pfrl_mlp_jvp(_ptr(x), M, K0, L, W, N, acts[0], S, VW, VB, _ptr(col_scale), _ptr(ty), int(small_m),
+                               stream), "mlp_jvp")
+        check(lib.pfrl_mlp_bwd(_ptr(x), M, K0, L, 1, W, N, acts, S, DY, None, G, WS, packed_n, stream), "mlp_bwd")
+        check(lib.pfrl_trpo_fvp_finish(_ptr(packed), packed_n, nseg, SRC, DST, LEN, _ptr(Hpp), P, p_off, V(base),
+                                       damping, n, _ptr(out), stream), "trpo_fvp_finish")
+        return out
+
+    fvp.keep = (x, weights, saved, col_scale, Hpp, packed, work)      # (what the launches read stays alive)
+    return fvp
+
+
+# ---------------------------------------------------------------------------------------------
 # whole wide MLPs as one launch: forward, and the frozen-parameter input gradient (csrc/mlp_wide.hip)
 # ---------------------------------------------------------------------------------------------
 MLP_WIDE_MAX_HIDDEN = 512

@@ -9,6 +9,8 @@ of the windows in microseconds per call for both variants, and the largest diffe
     python tools/mlp_time.py --pair              # policy and value function as a Branched (one launch for both)
     python tools/mlp_time.py --wide              # the wide route (csrc/mlp_wide.hip) against the per-layer launches,
                                                  # PFRL_MLP_WIDE=1 against 0, each as replays of a captured graph
+    python tools/mlp_time.py --fvp               # TRPO's Fisher-vector product: ops.gaussian_mlp_fisher (three or four
+                                                 # launches) against autograd's double backward, us per product
 """
 import argparse
 import copy
@@ -123,6 +125,47 @@ def wide_main(args):
         print(json.dumps(rec), flush=True)
 
 
+FVP_SHAPES = [(2048, 11, 3), (5000, 11, 3), (5000, 17, 6), (5000, 376, 17)]      # (rows, obs, A)
+
+
+def fvp_main(args):
+    """One damped product on a 64-64 tanh Gaussian policy (diagonal covariance, as train_trpo.py): the launches of
+    ops.gaussian_mlp_fisher against ``_hessian_vector_product`` on a KL graph built once, alternating windows."""
+    from pfrl_amd import ops
+    from pfrl_amd.agents import trpo
+
+    for rows, obs, A in FVP_SHAPES:
+        torch.manual_seed(0)
+        head = pfrl_amd.policies.GaussianHeadWithStateIndependentCovariance(
+            action_size=A, var_type="diagonal", var_func=lambda v: torch.exp(2 * v), var_param_init=0)
+        policy = nn.Sequential(*make(obs, A, nn.Tanh, False), head).cuda()
+        params = list(policy.parameters())
+        x = torch.randn(rows, obs, device="cuda")
+        vec = torch.randn(sum(p.numel() for p in params), device="cuda")
+        saved_cap, ops.FISHER_MAX_INPUT = ops.FISHER_MAX_INPUT, 1 << 62       # (time the shapes the cap may refuse too)
+        fused = ops.gaussian_mlp_fisher(policy, x, 0.01)
+        ops.FISHER_MAX_INPUT = saved_cap
+        with torch.no_grad():
+            old = policy(x)
+        kl = torch.mean(torch.distributions.kl_divergence(old, policy(x)))
+        flat = trpo._flat_grads([kl], params, create_graph=True)
+        fns = {"route": lambda: fused(vec),
+               "double_backward": lambda: trpo._hessian_vector_product(flat, params, vec) + 0.01 * vec}
+        outs = {k: f().clone() for k, f in fns.items()}
+        diff = float((outs["route"] - outs["double_backward"]).abs().max())
+        for f in fns.values():
+            window(f, 20)
+        calls = {k: max(5, int(args.window_ms * 1e3 / window(f, 20))) for k, f in fns.items()}
+        times = {k: [] for k in fns}
+        for _ in range(args.windows):
+            for k, f in fns.items():
+                times[k].append(window(f, calls[k]))
+        rec = dict(rows=rows, obs=obs, A=A, max_abs_diff=diff, max_abs=float(outs["double_backward"].abs().max()))
+        for k, v in times.items():
+            rec[k + "_us"] = dict(mean=sum(v) / len(v), min=min(v), max=max(v))
+        print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, nargs="+", default=[1, 64, 2048, 16384])
@@ -132,9 +175,12 @@ def main():
     ap.add_argument("--windows", type=int, default=10)
     ap.add_argument("--window-ms", type=float, default=20.0)
     ap.add_argument("--wide", action="store_true")
+    ap.add_argument("--fvp", action="store_true")
     args = ap.parse_args()
     if args.wide:
         return wide_main(args)
+    if args.fvp:
+        return fvp_main(args)
     act = nn.ReLU if args.relu else nn.Tanh
     for obs in args.obs:
         torch.manual_seed(0)
