@@ -1208,6 +1208,37 @@ int pfrl_mlp_bwd(const float *x, int32_t M, int32_t in_features, int32_t n_layer
                  const float *const *w, const int32_t *widths, const int32_t *act,
                  const float *const *saved, const float *const *dy, float *const *dx, float *const *grads,
                  float *const *slab_ws, int64_t slab_stride, void *stream);
+/* The same two launches behind an observation normaliser (EmpiricalNormalization.forward(x, update=False),
+ * pfrl/nn/empirical_normalization.py:90-107, in front of the networks of the MuJoCo set-ups): x is the RAW
+ * batch, and wherever the first layer's x chunk is staged (the forward's product, the backward's dW_0) every
+ * element is clamp((x - mean[k]) * scale[k], -clip, clip), clip <= 0: no clamp, with scale[k] =
+ * (float)(1 / sqrt((double)(var[k] + eps))), the bits of torch's (var + eps) ** -0.5 on the device.  mean / var
+ * [in_features] f32 are the module's buffers, read in place at launch time (a captured launch follows them);
+ * never read beyond in_features.  A subtract, a multiply and two compares, uncontracted: y, save and grads have
+ * the bits of pfrl_mlp_fwd / pfrl_mlp_bwd on the normalised batch, and the row-bits guarantee above holds
+ * with "the statistics" added.  No input gradient (observations need none): pfrl_mlp_bwd_norm has no dx.
+ * Refusals as above, and null or misaligned mean / var or eps < 0: PFRL_ERR_ARG, nothing is written. */
+int pfrl_mlp_fwd_norm(const float *x, int32_t M, int32_t in_features, int32_t n_layers, int32_t n_nets,
+                      const float *const *w, const float *const *b, const int32_t *widths, const int32_t *act,
+                      float *const *save, float *const *y, int32_t small_m, const float *mean, const float *var,
+                      float eps, float clip, void *stream);
+int pfrl_mlp_bwd_norm(const float *x, int32_t M, int32_t in_features, int32_t n_layers, int32_t n_nets,
+                      const float *const *w, const int32_t *widths, const int32_t *act,
+                      const float *const *saved, const float *const *dy, float *const *grads,
+                      float *const *slab_ws, int64_t slab_stride, const float *mean, const float *var, float eps,
+                      float clip, void *stream);
+/* Fold a batch into that normaliser's running statistics (EmpiricalNormalization.experience,
+ * pfrl/nn/empirical_normalization.py:63-88) as two launches (csrc/obsnorm.hip), in f64, no atomics, one order
+ * of every sum.  x [n][D] f32 contiguous, 0 <= n <= 65536, 1 <= D <= 512; mean / var [D] f32 and count (one
+ * int64) are the module's buffers, updated in place:
+ *   r = n / (count + n);  d = m_x - mean;  mean += r d;  var += r (v_x - var + d (m_x - mean_new))
+ * with m_x / v_x the batch's mean and biased variance per column (Welford / Chan in f64 over row slabs), each
+ * result rounded once to f32; count += n.  until >= 0: a call at count >= until writes nothing (the test is
+ * made on the device); until < 0: no limit.  ws: 8-byte aligned workspace of ws_doubles >=
+ * 2 D ceil(n / max(64, ceil(n / 64))) doubles, written before it is read.  n == 0: 0, nothing is written.
+ * Outside the envelope, null or misaligned pointers: PFRL_ERR_ARG, nothing is written. */
+int pfrl_obs_stats_update(const float *x, int32_t n, int32_t D, float *mean, float *var, int64_t *count,
+                          int64_t until, double *ws, int64_t ws_doubles, void *stream);
 /* The forward-mode tangent of ONE such network with respect to its parameters, the J v half of the
  * Gauss-Newton form J^T diag(col_scale) J of the Fisher-vector product (`_hessian_vector_product` of
  * pfrl/agents/trpo.py, called from trpo.py:557-598; J^T is pfrl_mlp_bwd).  Same envelope.  saved[l]: the

@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libpfrl_amd.so")
 # measurement hook (tools/build_variant.sh): another build of the same sources, e.g. other compiler
 # flags, loaded instead of the in-tree library.  Never set by the package, the tests or bench.py.
 _LIB_OVERRIDE = os.environ.get("PFRL_AMD_LIB")
-SOURCES = ["frames.hip", "replay.hip", "sumtree.hip", "rollout.hip", "optim.hip", "tdloss.hip", "operator_td.hip", "bias_act.hip", "noisy.hip", "c51.hip", "iqn.hip", "dueling.hip", "qnet.hip", "actor.hip", "actor_act.hip", "hostplan.hip", "philox.hip", "ppo_gaussian.hip", "trpo.hip", "reinforce.hip", "a2c.hip", "td3.hip", "naf.hip", "lstm.hip", "lstm_seq.hip", "gru.hip", "gru_seq.hip", "iqn_embed.hip", "mlp.hip", "mlp_wide.hip"]
+SOURCES = ["frames.hip", "replay.hip", "sumtree.hip", "rollout.hip", "optim.hip", "tdloss.hip", "operator_td.hip", "bias_act.hip", "noisy.hip", "c51.hip", "iqn.hip", "dueling.hip", "qnet.hip", "actor.hip", "actor_act.hip", "hostplan.hip", "philox.hip", "ppo_gaussian.hip", "trpo.hip", "reinforce.hip", "a2c.hip", "td3.hip", "naf.hip", "lstm.hip", "lstm_seq.hip", "gru.hip", "gru_seq.hip", "iqn_embed.hip", "mlp.hip", "mlp_wide.hip", "obsnorm.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     # the parity contract is one correctly rounded IEEE op per source op
@@ -268,6 +268,9 @@ EXPORTS = {
     "pfrl_mlp_bwd_slabs": (ctypes.c_int, "i"),
     "pfrl_mlp_bwd": (ctypes.c_int, "piiiippppppppqp"),
     "pfrl_mlp_jvp": (ctypes.c_int, "piiippipppppip"),
+    "pfrl_mlp_fwd_norm": (ctypes.c_int, "piiiippppppippffp"),
+    "pfrl_mlp_bwd_norm": (ctypes.c_int, "piiiipppppppqppffp"),
+    "pfrl_obs_stats_update": (ctypes.c_int, "piipppqpqp"),
     "pfrl_mlp_wide_fwd": (ctypes.c_int, "ppiiiiipppippp"),
     "pfrl_mlp_wide_dx": (ctypes.c_int, "iiiippipppiip"),
     "pfrl_philox_normal": (ctypes.c_int, "QQipppppip"),

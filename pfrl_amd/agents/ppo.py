@@ -296,17 +296,18 @@ class _ActGraph:
 
     def _body(self, refs, into=None):
         ag = self.agent
-        b_state = ag._features(refs)
         split = self._split()
         gauss = self.gaussian_act_split() if split is None else None
-        if gauss is not None:
+        if gauss is None:
+            b_state = ag._features(refs)
+        else:
             # Gaussian policy: the draws are torch.randn's -- what Normal.sample's torch.normal
             # starts from, at the generator offsets it would use -- scaled and shifted, with the
             # entropy, in one launch: the action stream of the eager path bit for bit
             assert into is None
             view, head = gauss
             with torch.no_grad(), evaluating(ag.model):
-                mean, value = view(b_state)
+                mean, value = ag._forward_refs(view, refs)
                 z = torch.randn(mean.shape, dtype=torch.float32, device=mean.device)
                 action, entropy = ops.ppo_gaussian_act(mean, self.gaussian_scale(head, mean.shape[1]),
                                                        z=z)
@@ -607,22 +608,32 @@ class PPO(agent.AttributeSavingMixin, agent.BatchAgent):
             x = self._normalize(x)
         return x
 
-    def _normalize(self, x):
-        """``obs_normalizer(x, update=False)``.  While a graph is being captured the statistics are
-        read IN PLACE: the module caches ``(var + eps) ** -0.5`` in a tensor that it drops whenever
-        the statistics learn, and a graph that had baked that tensor's address in would keep
-        normalising with the statistics of the rollout it was captured in.  Same expression, same
-        bits (nn/empirical_normalization.py ``forward``)."""
-        from pfrl_amd.nn import EmpiricalNormalization
+    def _forward_refs(self, net, refs_dev):
+        """``net(self._features(refs_dev))``.  With an ``obs_normalizer`` and a ``net`` that is a fused
+        small-MLP container (nn/mfma_linear.py ``forward_normalized``) the RAW gathered batch goes in
+        and the whole-MLP launch normalises it in its loader: the same bits without the five
+        elementwise launches in front (``PFRL_OBS_NORM_LOADER=0``, or a launch that cannot take the
+        normaliser: normalised in front, as ``_features`` does)."""
+        from pfrl_amd.nn import Branched
 
-        n = self.obs_normalizer
-        if not (type(n) is EmpiricalNormalization and x.is_cuda
-                and torch.cuda.is_current_stream_capturing()):
-            return n(x, update=False)
-        y = (x - n._mean) * (n._var + n.eps) ** -0.5
-        if n.clip_threshold is not None:
-            y = torch.clamp(y, -n.clip_threshold, n.clip_threshold)
-        return y
+        fns = [getattr(net, "forward_normalized", None)]
+        if type(net) is Branched:
+            # (TRPO's ``Branched(policy, vf)``: a plain container of two fused ones, a launch each)
+            fns = [getattr(kid, "forward_normalized", None) for kid in net.child_modules]
+        with torch.no_grad():
+            raw = self.obs_normalizer is not None and None not in fns
+            x = self._gather(refs_dev) if raw else self._features(refs_dev)
+        if not raw:
+            return net(x)
+        outs = tuple(fn(x, self.obs_normalizer) for fn in fns)
+        return outs if type(net) is Branched else outs[0]
+
+    def _normalize(self, x):
+        """``obs_normalizer(x, update=False)``; under graph capture on the statistics in place
+        (nn/empirical_normalization.py ``_normalize_with_current``)."""
+        from pfrl_amd.nn.empirical_normalization import _normalize_with_current
+
+        return _normalize_with_current(self.obs_normalizer, x)
 
     # -- acting --------------------------------------------------------------------
     def _sample_action(self, action_distrib):
@@ -810,18 +821,18 @@ class PPO(agent.AttributeSavingMixin, agent.BatchAgent):
         with torch.no_grad(), evaluating(self.model):
             for lo in range(0, M, self.value_pass_chunk):
                 hi = min(M, lo + self.value_pass_chunk)
-                x = self._features(refs_dev[lo:hi])
                 if gauss is not None:
                     # Gaussian policy: log pi(a | s) in one launch behind the head-less model,
                     # written straight into the column
                     view, head = gauss
-                    mean, vs = view(x)
+                    mean, vs = self._forward_refs(view, refs_dev[lo:hi])
                     values[lo:hi] = vs.reshape(-1)
                     if actions_dev is not None:
                         ops.ppo_gaussian_act(mean, self._act_graph.gaussian_scale(head, mean.shape[1]),
                                              given_action=actions_dev[lo:hi],
                                              out_log_prob=log_probs[lo:hi])
                     continue
+                x = self._features(refs_dev[lo:hi])
                 if split is not None:
                     # heads + log pi(a | s) + V(s) in one launch behind the trunk (the acting path's
                     # kernel without the draw), written straight into the columns
@@ -1123,16 +1134,19 @@ class PPO(agent.AttributeSavingMixin, agent.BatchAgent):
             mb = ops.ppo_minibatch(batch["idx"], c["adv"], c["mean_std"], self.standardize_advantages,
                                    c["log_prob"], c["v_pred"], c["v_teacher"], c["action"],
                                    c["s_refs"])
-            states = self._features(mb["refs"])
+            gauss = self._gaussian_loss_split() if mb["action"].dtype == torch.float32 else None
+            # (a Gaussian policy behind a normaliser: the raw batch, normalised by the launch -- below)
+            states = (None if gauss is not None and self.obs_normalizer is not None
+                      else self._features(mb["refs"]))
         fused = self._fused_loss_split()
-        gauss = self._gaussian_loss_split() if mb["action"].dtype == torch.float32 else None
         if gauss is not None:
             # Gaussian policy: mean and value from the head-less model, the scale vector by torch
             # (any var_func), then loss + its gradient with respect to all three in ONE launch
             # (pfrl_ppo_gaussian_loss) instead of torch.distributions + autograd; backward starts
             # at the three
             view, head = gauss
-            mean, vs_pred = view(states)
+            mean, vs_pred = (view(states) if states is not None
+                             else self._forward_refs(view, mb["refs"]))
             scale = self._act_graph.gaussian_scale(head, mean.shape[1])
             self.optimizer.zero_grad(set_to_none=True)
             out4, dmean, dvalue, dscale = ops.ppo_gaussian_loss(

@@ -496,9 +496,7 @@ class TRPO(PPO):
     def _vf_step(self, batch, cols=None):
         c = self._vf_cols if cols is None else cols
         idx = batch["idx"]
-        with torch.no_grad():
-            states = self._features(c["s_refs"][idx])
-        loss = F.mse_loss(self.vf(states), c["v_teacher"][idx][..., None])
+        loss = F.mse_loss(self._forward_refs(self.vf, c["s_refs"][idx]), c["v_teacher"][idx][..., None])
         self.vf_optimizer.zero_grad(set_to_none=True)
         loss.backward()
         if self.max_grad_norm is not None:

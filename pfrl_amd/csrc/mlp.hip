@@ -37,6 +37,12 @@
 // entry point (the f32 adds of pfrl_splitk_reduce missed the accuracy rule of the tests for bias
 // gradients).  No atomics; one order of every sum.
 //
+// Normalised input (the NORM instantiations behind pfrl_mlp_fwd_norm / pfrl_mlp_bwd_norm: an observation normaliser
+// in front of the first layer).  x is the raw batch; the one place where each kernel stages the first layer's x
+// chunk (the forward's product, the backward's dW_0 operand) normalises on the way into LDS (stage_x), so y, the
+// hidden saves and the packed gradient have the bits of the plain launches on the normalised batch and the
+// row-bits rule above holds with "the statistics" added.  No dx with a normaliser; the tangent pass takes none.
+//
 // Tangent pass (k_mlp_jvp: J v of the last layer's output with respect to the parameters, the forward-mode
 // half of a Gauss-Newton / Fisher-vector product whose other half, J^T, is the backward above).  With the
 // direction V_l, c_l shaped like W_l, b_l and the hidden activations a_l that the forward saved:
@@ -93,6 +99,44 @@ struct BwdArgs {
     BwdNet net[2];
 };
 
+// The observation normaliser in front of the first layer (pfrl_mlp_fwd_norm / pfrl_mlp_bwd_norm): the running
+// mean and variance [K0], read in place; clip <= 0: none.
+struct NormArgs {
+    const float *mean, *var;
+    float eps, clip;
+};
+
+// The first layer's x chunk into LDS.  NORM: every element as clamp((x - mean[k]) * scale[k], +-clip) with
+// scale = (float)(1 / sqrt((double)(var + eps))), the f32 sum widened: on this device the bits of torch's
+// (var + eps) ** -0.5 (rsqrtf, 1.f / sqrtf, powf and v_rsq_f32 itself all differ from it in 11 to 26 % of a million
+// values; tests/test_mlp_norm.py holds the expression to torch's).  Then a subtract, a multiply and two compares
+// (no contraction: the build has it off): the bits of the module's own expression.  A thread's column is the same
+// in every trip of the staging loop (kThreads is a multiple of 64), so the column's mean and scale live in two
+// registers, loaded once per chunk beside the first x loads: no LDS array, no barrier between the statistics and
+// the tile.  Rows beyond M and columns beyond K0 stay zeros; mean and var are never read beyond K0.
+template <bool NORM>
+__device__ __forceinline__ void stage_x(Tile *dst, const float *__restrict__ x, int rows, int r0, int M, int c0, int K0,
+                                        const NormArgs &nm, int tid) {
+    if constexpr (!NORM) {
+        stage<kThreads>(dst, x, rows, r0, M, c0, K0, K0, tid);
+    } else {
+        static_assert(kThreads % 64 == 0, "a thread keeps one column");
+        const int c = tid & 63, gc = c0 + c;
+        const bool in = gc < K0;
+        const float mu = in ? nm.mean[gc] : 0.f;
+        const float sc = in ? (float)(1.0 / sqrt((double)(nm.var[gc] + nm.eps))) : 0.f;
+        const float clip = nm.clip;
+        for (int r = tid >> 6; r < rows; r += kThreads / 64) {
+            float v = 0.f;
+            if (in && r0 + r < M) {
+                v = (x[(size_t)(r0 + r) * K0 + gc] - mu) * sc;
+                if (clip > 0.f) v = v < -clip ? -clip : (v > clip ? clip : v);
+            }
+            dst[r][c] = v;
+        }
+    }
+}
+
 // acc[j] += A[arow + c16][0 .. kpad) . W[16 ct(j) + c16][0 .. kpad): NT column tiles against one row tile
 template <int RT>
 __device__ __forceinline__ void fwd_mma(f32x4 (&acc)[RT / 16], const Tile *sA, const Tile *sW, int kpad, int ntiles,
@@ -141,9 +185,9 @@ __device__ __forceinline__ void fwd_epilogue(const f32x4 (&acc)[RT / 16], Tile *
     }
 }
 
-template <int RT>
+template <int RT, bool NORM>
 __global__ __launch_bounds__(kThreads) PFRL_NO_PACKED_FP32 void k_mlp_fwd(const float *__restrict__ x, FwdArgs args,
-                                                                         int M, int K0, int L) {
+                                                                         int M, int K0, int L, NormArgs nm) {
     __shared__ __attribute__((aligned(16))) float sA[RT][kLd];
     __shared__ __attribute__((aligned(16))) float sW[2][kMaxW][kLd];
     const FwdNet &net = args.net[blockIdx.y];
@@ -163,7 +207,7 @@ __global__ __launch_bounds__(kThreads) PFRL_NO_PACKED_FP32 void k_mlp_fwd(const 
         for (int j = 0; j < NT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int c0 = 0; c0 < K0; c0 += kChunk) {
             __syncthreads();                                  // (the previous chunk has been read)
-            stage<kThreads>(sA, x, RT, row0, M, c0, K0, K0, tid);
+            stage_x<NORM>(sA, x, RT, row0, M, c0, K0, nm, tid);
             stage<kThreads>(sW[0], net.w[0], 16 * nt, 0, N, c0, K0, K0, tid);
             __syncthreads();
             fwd_mma<RT>(acc, sA, sW[0], (min(kChunk, K0 - c0) + 15) & ~15, nt, wave, c16, kq);
@@ -352,9 +396,10 @@ __device__ __forceinline__ void store_wtile(float *__restrict__ dst, const f64x4
     }
 }
 
+template <bool NORM>
 __global__ __launch_bounds__(kThreads) PFRL_NO_PACKED_FP32 void k_mlp_bwd(const float *__restrict__ x, BwdArgs args,
                                                                          int M, int K0, int L, int tiles_per_wg,
-                                                                         long long slab_stride) {
+                                                                         long long slab_stride, NormArgs nm) {
     __shared__ __attribute__((aligned(16))) float sD[kBwdRows][kLd];
     __shared__ __attribute__((aligned(16))) float sA[kBwdRows][kLd];
     __shared__ __attribute__((aligned(16))) float sW[kMaxW][kLd];
@@ -412,7 +457,7 @@ __global__ __launch_bounds__(kThreads) PFRL_NO_PACKED_FP32 void k_mlp_bwd(const 
             const int c0 = c * kChunk, ntk = min(4, (K0 - c0 + 15) >> 4);
             __syncthreads();
             if (c == 0 && L == 1) stage<kThreads>(sD, net.dy, kBwdRows, row0, M, 0, N, N, tid);
-            stage<kThreads>(sA, x, kBwdRows, row0, M, c0, K0, K0, tid);
+            stage_x<NORM>(sA, x, kBwdRows, row0, M, c0, K0, nm, tid);
             if (net.dx != nullptr) stage<kThreads>(sW, net.w[0], 16 * ntn, 0, N, c0, K0, K0, tid);
             __syncthreads();
             if (wave < ntn) bwd_wgrad(gw0[c], c == 0 ? &gb[0] : nullptr, sD, sA, ntk, wave, c16, kq);
@@ -497,11 +542,17 @@ const char *check_envelope(const float *x, int32_t M, int32_t K0, int32_t L, int
     return nullptr;
 }
 
-}  // namespace
+// the normaliser's arguments (nm == nullptr: none)
+const char *check_norm(const float *mean, const float *var, float eps) {
+    if (mean == nullptr || var == nullptr) return "normaliser: null pointer";
+    if (!aligned4(mean) || !aligned4(var)) return "normaliser: misaligned pointer";
+    if (!(eps >= 0.f)) return "normaliser: eps >= 0";
+    return nullptr;
+}
 
-extern "C" int pfrl_mlp_fwd(const float *x, int32_t M, int32_t in_features, int32_t n_layers, int32_t n_nets,
-                            const float *const *w, const float *const *b, const int32_t *widths, const int32_t *act,
-                            float *const *save, float *const *y, int32_t small_m, void *stream) {
+int mlp_fwd(const float *x, int32_t M, int32_t in_features, int32_t n_layers, int32_t n_nets, const float *const *w,
+            const float *const *b, const int32_t *widths, const int32_t *act, float *const *save, float *const *y,
+            int32_t small_m, const NormArgs *norm, void *stream) {
     if (n_nets == 0) return 0;
     const char *err = check_envelope(x, M, in_features, n_layers, n_nets, w, widths, act);
     PFRL_CHECK_ARG(err == nullptr, err);
@@ -524,13 +575,33 @@ extern "C" int pfrl_mlp_fwd(const float *x, int32_t M, int32_t in_features, int3
         PFRL_CHECK_ARG(n.y != nullptr && aligned4(n.y), "pfrl_mlp_fwd: null or misaligned output");
     }
     const int lim = small_m < 0 ? kSmallM : small_m;
-    if (M <= lim)
-        hipLaunchKernelGGL(k_mlp_fwd<16>, dim3((M + 15) / 16, n_nets), dim3(kThreads), 0, (hipStream_t)stream, x, a,
-                           (int)M, (int)in_features, (int)n_layers);
-    else
-        hipLaunchKernelGGL(k_mlp_fwd<64>, dim3((M + 63) / 64, n_nets), dim3(kThreads), 0, (hipStream_t)stream, x, a,
-                           (int)M, (int)in_features, (int)n_layers);
+    const bool small = M <= lim;
+    const dim3 grid((M + (small ? 15 : 63)) / (small ? 16 : 64), n_nets);
+    const NormArgs nm = norm != nullptr ? *norm : NormArgs{};
+    auto kernel = norm != nullptr ? (small ? k_mlp_fwd<16, true> : k_mlp_fwd<64, true>)
+                                  : (small ? k_mlp_fwd<16, false> : k_mlp_fwd<64, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, (hipStream_t)stream, x, a, (int)M, (int)in_features,
+                       (int)n_layers, nm);
     PFRL_LAUNCH_CHECK();
+}
+
+}  // namespace
+
+extern "C" int pfrl_mlp_fwd(const float *x, int32_t M, int32_t in_features, int32_t n_layers, int32_t n_nets,
+                            const float *const *w, const float *const *b, const int32_t *widths, const int32_t *act,
+                            float *const *save, float *const *y, int32_t small_m, void *stream) {
+    return mlp_fwd(x, M, in_features, n_layers, n_nets, w, b, widths, act, save, y, small_m, nullptr, stream);
+}
+
+extern "C" int pfrl_mlp_fwd_norm(const float *x, int32_t M, int32_t in_features, int32_t n_layers, int32_t n_nets,
+                                 const float *const *w, const float *const *b, const int32_t *widths,
+                                 const int32_t *act, float *const *save, float *const *y, int32_t small_m,
+                                 const float *mean, const float *var, float eps, float clip, void *stream) {
+    if (n_nets == 0) return 0;
+    const char *err = check_norm(mean, var, eps);
+    PFRL_CHECK_ARG(err == nullptr, err);
+    const NormArgs nm{mean, var, eps, clip};
+    return mlp_fwd(x, M, in_features, n_layers, n_nets, w, b, widths, act, save, y, small_m, &nm, stream);
 }
 
 extern "C" int pfrl_mlp_jvp(const float *x, int32_t M, int32_t in_features, int32_t n_layers, const float *const *w,
@@ -575,10 +646,12 @@ extern "C" int pfrl_mlp_bwd_slabs(int32_t M) {
     return (tiles + per_wg - 1) / per_wg;
 }
 
-extern "C" int pfrl_mlp_bwd(const float *x, int32_t M, int32_t in_features, int32_t n_layers, int32_t n_nets,
-                            const float *const *w, const int32_t *widths, const int32_t *act,
-                            const float *const *saved, const float *const *dy, float *const *dx,
-                            float *const *grads, float *const *slab_ws, int64_t slab_stride, void *stream) {
+namespace {
+
+int mlp_bwd(const float *x, int32_t M, int32_t in_features, int32_t n_layers, int32_t n_nets, const float *const *w,
+            const int32_t *widths, const int32_t *act, const float *const *saved, const float *const *dy,
+            float *const *dx, float *const *grads, float *const *slab_ws, int64_t slab_stride, const NormArgs *norm,
+            void *stream) {
     if (n_nets == 0) return 0;
     const char *err = check_envelope(x, M, in_features, n_layers, n_nets, w, widths, act);
     PFRL_CHECK_ARG(err == nullptr, err);
@@ -616,11 +689,35 @@ extern "C" int pfrl_mlp_bwd(const float *x, int32_t M, int32_t in_features, int3
                        "pfrl_mlp_bwd: slab stride below the packed gradient's length or no multiple of 4");
     }
     const int tiles = (M + kBwdRows - 1) / kBwdRows;
-    hipLaunchKernelGGL(k_mlp_bwd, dim3(slabs, n_nets), dim3(kThreads), 0, (hipStream_t)stream, x, a, (int)M,
-                       (int)in_features, (int)n_layers, (tiles + slabs - 1) / slabs,
-                       (long long)(slabs == 1 ? 0 : slab_stride));
+    const NormArgs nm = norm != nullptr ? *norm : NormArgs{};
+    hipLaunchKernelGGL(norm != nullptr ? k_mlp_bwd<true> : k_mlp_bwd<false>, dim3(slabs, n_nets), dim3(kThreads), 0,
+                       (hipStream_t)stream, x, a, (int)M, (int)in_features, (int)n_layers, (tiles + slabs - 1) / slabs,
+                       (long long)(slabs == 1 ? 0 : slab_stride), nm);
     if (slabs > 1)
         hipLaunchKernelGGL(k_mlp_fold, dim3((max_floats + kThreads - 1) / kThreads, n_nets), dim3(kThreads), 0,
                            (hipStream_t)stream, f, slabs, (long long)slab_stride);
     PFRL_LAUNCH_CHECK();
+}
+
+}  // namespace
+
+extern "C" int pfrl_mlp_bwd(const float *x, int32_t M, int32_t in_features, int32_t n_layers, int32_t n_nets,
+                            const float *const *w, const int32_t *widths, const int32_t *act,
+                            const float *const *saved, const float *const *dy, float *const *dx,
+                            float *const *grads, float *const *slab_ws, int64_t slab_stride, void *stream) {
+    return mlp_bwd(x, M, in_features, n_layers, n_nets, w, widths, act, saved, dy, dx, grads, slab_ws, slab_stride,
+                   nullptr, stream);
+}
+
+extern "C" int pfrl_mlp_bwd_norm(const float *x, int32_t M, int32_t in_features, int32_t n_layers, int32_t n_nets,
+                                 const float *const *w, const int32_t *widths, const int32_t *act,
+                                 const float *const *saved, const float *const *dy, float *const *grads,
+                                 float *const *slab_ws, int64_t slab_stride, const float *mean, const float *var,
+                                 float eps, float clip, void *stream) {
+    if (n_nets == 0) return 0;
+    const char *err = check_norm(mean, var, eps);
+    PFRL_CHECK_ARG(err == nullptr, err);
+    const NormArgs nm{mean, var, eps, clip};
+    return mlp_bwd(x, M, in_features, n_layers, n_nets, w, widths, act, saved, dy, nullptr, grads, slab_ws, slab_stride,
+                   &nm, stream);
 }

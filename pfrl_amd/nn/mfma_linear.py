@@ -28,6 +28,7 @@ from pfrl_amd import _native
 from pfrl_amd._native import check
 from pfrl_amd.nn import mfma_trunk as _t
 from pfrl_amd.nn.branched import Branched
+from pfrl_amd.nn.empirical_normalization import _normalize_with_current
 from pfrl_amd.nn.mfma_trunk import _ceil_div, _p, _stream
 
 _ENABLED = os.environ.get("PFRL_MFMA_LINEAR", "1") != "0"
@@ -498,26 +499,55 @@ class _FusedMlpSequential(_MlpSequential):
             return _run_children(mods[s:], x)
         return _run_children(mods[e:], ops.mlp_fused(x, layers, act))
 
+    def forward_normalized(self, x, normalizer):
+        """``self(normalizer(x, update=False))`` on the RAW observations ``x``: where the stretch starts at
+        the first child and ``ops.mlp_fused_supported(..., in_norm=normalizer)``, the launch normalises in
+        its loader (same bits); otherwise the normaliser runs in front as torch launches and ``forward``
+        follows.  Exactly one of the two, always."""
+        from pfrl_amd import ops
+
+        mods = list(self._modules.values())
+        run = _find_mlp_run(mods) if _mlp_route_open(self) else None
+        if run is not None and run[0] == 0:
+            layers = [(m.weight, m.bias) for m in mods[:run[1]:2]]
+            if ops.mlp_fused_supported(x, layers, run[2], in_norm=normalizer):
+                return _run_children(mods[run[1]:], ops.mlp_fused(x, layers, run[2], in_norm=normalizer))
+        return self.forward(_normalize_with_current(normalizer, x))
+
 
 class _FusedBranched(Branched):
     """A ``Branched`` (same children) of two ``_FusedMlpSequential`` that begin with stretches of
     equal depth: both stretches as ONE launch on the shared input, then what follows in each."""
 
     def forward(self, *args, **kwargs):
+        if len(args) == 1 and not kwargs:
+            out = self._both(args[0], None)
+            if out is not None:
+                return out
+        return Branched.forward(self, *args, **kwargs)
+
+    def forward_normalized(self, x, normalizer):
+        """``self(normalizer(x, update=False))`` on the RAW observations ``x`` (see
+        ``_FusedMlpSequential.forward_normalized``): the one launch of both stretches normalises in its
+        loader where it can; otherwise the normaliser runs once in front of ``forward``."""
+        out = self._both(x, normalizer)
+        return self.forward(_normalize_with_current(normalizer, x)) if out is None else out
+
+    def _both(self, x, norm):
+        """Both stretches as one launch on ``x`` (normalised by the launch with ``norm``), or None."""
         from pfrl_amd import ops
 
         kids = list(self.child_modules)
-        if (len(args) == 1 and not kwargs and len(kids) == 2
-                and all(type(k) is _FusedMlpSequential and _mlp_route_open(k) for k in kids)):
+        if len(kids) == 2 and all(type(k) is _FusedMlpSequential and _mlp_route_open(k) for k in kids):
             mods = [list(k._modules.values()) for k in kids]
             runs = [_find_mlp_run(m) for m in mods]
             if all(r is not None and r[0] == 0 for r in runs) and runs[0][1] == runs[1][1]:
                 layers = [[(m.weight, m.bias) for m in ms[:r[1]:2]] for ms, r in zip(mods, runs)]
                 acts = (runs[0][2], runs[1][2])
-                if ops.mlp_fused_supported(args[0], layers, acts):
-                    ys = ops.mlp_fused(args[0], layers, acts)
+                if ops.mlp_fused_supported(x, layers, acts, in_norm=norm):
+                    ys = ops.mlp_fused(x, layers, acts, in_norm=norm)
                     return tuple(_run_children(ms[r[1]:], y) for ms, r, y in zip(mods, runs, ys))
-        return Branched.forward(self, *args, **kwargs)
+        return None
 
 
 def _fuse_small_mlps(model, first_order=True):

@@ -2071,11 +2071,13 @@ def _mlp_nets(layers, act):
 
 
 class _MlpFused(torch.autograd.Function):
-    """meta = (acts, n_layers, small_m); params = w, b of every layer, network after network."""
+    """meta = (acts, n_layers, small_m, norm); params = w, b of every layer, network after network.  norm:
+    None, or (mean, var, eps, clip) of an observation normaliser in front of the first layer: x is then the
+    raw batch (saved as it is) and both launches normalise it in their loaders."""
 
     @staticmethod
     def forward(ctx, x, meta, *params):
-        acts, L, small_m = meta
+        acts, L, small_m, norm = meta
         nn_, (M, K0), dev = len(acts), x.shape, x.device
         train = any(ctx.needs_input_grad)
         V, I = ctypes.c_void_p, ctypes.c_int32
@@ -2091,7 +2093,12 @@ class _MlpFused(torch.autograd.Function):
                     S[2 * k + l] = saves[-1].data_ptr()
             ys.append(torch.empty((M, params[2 * (k * L + L - 1)].shape[0]), dtype=torch.float32, device=dev))
             Y[k] = ys[-1].data_ptr()
-        check(_native.lib().pfrl_mlp_fwd(_ptr(x), M, K0, L, nn_, W, B, N, A, S, Y, small_m, _stream()), "mlp_fwd")
+        if norm is None:
+            check(_native.lib().pfrl_mlp_fwd(_ptr(x), M, K0, L, nn_, W, B, N, A, S, Y, small_m, _stream()), "mlp_fwd")
+        else:
+            mean, var, eps, clip = norm
+            check(_native.lib().pfrl_mlp_fwd_norm(_ptr(x), M, K0, L, nn_, W, B, N, A, S, Y, small_m, _ptr(mean),
+                                                  _ptr(var), eps, clip, _stream()), "mlp_fwd_norm")
         if train:
             ctx.save_for_backward(x, *params, *saves)
             ctx.meta = meta
@@ -2100,7 +2107,7 @@ class _MlpFused(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, *dys):
-        acts, L, _ = ctx.meta
+        acts, L, _, norm = ctx.meta
         nn_ = len(acts)
         x, params, saves = ctx.saved_tensors[0], ctx.saved_tensors[1:1 + 2 * nn_ * L], ctx.saved_tensors[1 + 2 * nn_ * L:]
         (M, K0), dev, lib = x.shape, x.device, _native.lib()
@@ -2134,8 +2141,14 @@ class _MlpFused(torch.autograd.Function):
             G[k] = outs[k].data_ptr()
             if slabs > 1:
                 WS[k] = work[k].data_ptr()
-        check(lib.pfrl_mlp_bwd(_ptr(x), M, K0, L, nn_, W, N, A, S, DY, DX if need_dx else None, G, WS, stride,
-                               _stream()), "mlp_bwd")
+        if norm is None:
+            check(lib.pfrl_mlp_bwd(_ptr(x), M, K0, L, nn_, W, N, A, S, DY, DX if need_dx else None, G, WS, stride,
+                                   _stream()), "mlp_bwd")
+        else:
+            assert not need_dx
+            mean, var, eps, clip = norm
+            check(lib.pfrl_mlp_bwd_norm(_ptr(x), M, K0, L, nn_, W, N, A, S, DY, G, WS, stride, _ptr(mean), _ptr(var),
+                                        eps, clip, _stream()), "mlp_bwd_norm")
         grads = []
         for k in range(nn_):
             off = 0
@@ -2152,14 +2165,35 @@ class _MlpFused(torch.autograd.Function):
         return (dx, None) + tuple(grads)
 
 
-def mlp_fused_supported(x, layers, act):
+def obs_norm_loader_enabled():
+    """``PFRL_OBS_NORM_LOADER=0`` turns the normalised-input loaders of the whole-MLP launches off (read at every
+    call): the normaliser then runs as torch launches in front of them."""
+    return os.environ.get("PFRL_OBS_NORM_LOADER", "1") != "0"
+
+
+def _in_norm_ok(x, n):
+    """``n`` can ride in the loaders of the launches on ``x``: an ``EmpiricalNormalization`` of exactly that
+    class, float32, batch axis 0, buffers [1, in_features] on ``x``'s device; ``x`` needs no gradient."""
+    from pfrl_amd.nn.empirical_normalization import EmpiricalNormalization
+
+    return (type(n) is EmpiricalNormalization and obs_norm_loader_enabled() and n.batch_axis == 0
+            and not x.requires_grad
+            and all(t.dtype == torch.float32 and t.device == x.device and t.is_contiguous()
+                    and tuple(t.shape) == (1, x.shape[1]) for t in (n._mean, n._var)))
+
+
+def mlp_fused_supported(x, layers, act, in_norm=None):
     """Inside the envelope of :func:`mlp_fused` (csrc/mlp.hip refuses the rest): one network, or two of
     equal depth on the same ``x``; 1 to 3 ``(weight, bias)`` layers each, every width 1 .. 64 behind
     1 .. 512 inputs, ``act`` "tanh" or "relu"; ``x`` [1 .. 65536, in_features]; everything float32,
     contiguous and on ``x``'s CUDA device; a differentiated call of at most ``MLP_MAX_TRAIN_INPUT`` input
-    elements (above, the backward launch loses to the library).  ``PFRL_MLP_FUSED=0`` answers False."""
+    elements (above, the backward launch loses to the library).  ``PFRL_MLP_FUSED=0`` answers False.
+    ``in_norm``: an observation normaliser to apply to ``x`` in the launches' loaders (``_in_norm_ok``;
+    ``PFRL_OBS_NORM_LOADER=0`` answers False)."""
     if not (mlp_fused_enabled() and torch.is_tensor(x) and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32
             and x.is_contiguous() and 1 <= x.shape[0] <= MLP_MAX_ROWS and 1 <= x.shape[1] <= MLP_MAX_IN):
+        return False
+    if in_norm is not None and not _in_norm_ok(x, in_norm):
         return False
     nets, acts = _mlp_nets(layers, act)
     if not (1 <= len(nets) <= 2 and len(acts) == len(nets) and all(a in MLP_ACTS for a in acts)
@@ -2180,18 +2214,69 @@ def mlp_fused_supported(x, layers, act):
     return _native.available()
 
 
-def mlp_fused(x, layers, act, small_m=-1):
+def mlp_fused(x, layers, act, small_m=-1, in_norm=None):
     """``Linear, act, ..., Linear`` on ``x`` [M, in_features] as ONE HIP launch, and its backward as one
     (two above 64 rows: the fold of the gradient slabs).  ``layers``: the ``(weight, bias)`` pairs of
     one network with ``act`` "tanh" or "relu" -> y; or a pair of such lists with a pair of activations
     (two networks of equal depth on the same ``x``, e.g. policy and value function) -> (y0, y1).  The
     bits of a row of y depend on that row and the parameters only.  ``small_m``: up to this many rows
-    take the 16-row tile program (default: the launcher's).  Differentiable once."""
-    assert mlp_fused_supported(x, layers, act)
+    take the 16-row tile program (default: the launcher's).  Differentiable once.  ``in_norm``: an
+    ``EmpiricalNormalization``; ``x`` is then the RAW batch and the result has the bits of
+    ``mlp_fused(in_norm(x, update=False), ...)``: the launches read the module's buffers in place and normalise
+    in their loaders (the module's cached inverse deviation is not used: a captured launch follows the buffers)."""
+    assert mlp_fused_supported(x, layers, act, in_norm)
     nets, acts = _mlp_nets(layers, act)
     params = [t for net in nets for wb in net for t in wb]
-    out = _MlpFused.apply(x, (tuple(MLP_ACTS[a] for a in acts), len(nets[0]), int(small_m)), *params)
+    norm = None
+    if in_norm is not None:
+        clip = in_norm.clip_threshold
+        norm = (in_norm._mean, in_norm._var, float(in_norm.eps), 0.0 if clip is None else float(clip))
+    out = _MlpFused.apply(x, (tuple(MLP_ACTS[a] for a in acts), len(nets[0]), int(small_m), norm), *params)
     return out[0] if isinstance(act, str) else out
+
+
+# ---------------------------------------------------------------------------------------------
+# an observation normaliser's statistics learn from a batch in two launches (csrc/obsnorm.hip)
+# ---------------------------------------------------------------------------------------------
+OBS_STATS_MAX_ROWS = 65536
+OBS_STATS_MAX_DIM = 512
+
+
+def obs_stats_enabled():
+    """``PFRL_OBS_STATS_KERNEL=0`` keeps ``EmpiricalNormalization.experience`` on its torch expressions (read
+    at every call)."""
+    return os.environ.get("PFRL_OBS_STATS_KERNEL", "1") != "0"
+
+
+def obs_stats_supported(x, mean, var, count):
+    """``x`` [0 .. 65536, 1 .. 512] float32 contiguous on a CUDA device; ``mean`` / ``var`` float32 contiguous
+    with ``x.shape[1]`` elements and ``count`` one int64, on that device."""
+    return (torch.is_tensor(x) and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous()
+            and x.shape[0] <= OBS_STATS_MAX_ROWS and 1 <= x.shape[1] <= OBS_STATS_MAX_DIM
+            and all(t.device == x.device and t.dtype == torch.float32 and t.is_contiguous()
+                    and t.numel() == x.shape[1] for t in (mean, var))
+            and count.device == x.device and count.dtype == torch.int64 and count.numel() == 1
+            and _native.available())
+
+
+def obs_stats_update(x, mean, var, count, until=None, workspace=None):
+    """Fold the batch ``x`` [n, D] into the running ``mean`` / ``var`` [D] and ``count`` of an
+    ``EmpiricalNormalization``, in place, by the module's rule evaluated in float64 and rounded once
+    (pfrl_obs_stats_update: two launches, fixed summation order, nothing read back).  ``until``: a call at
+    ``count >= until`` changes nothing -- decided on the device.  ``workspace``: float64 scratch of at least
+    ``2 * D * slabs`` elements (default: a fresh one; every element read is written first)."""
+    assert obs_stats_supported(x, mean, var, count)
+    n, D = x.shape
+    if n == 0:
+        return
+    per = max(64, -(-n // 64))
+    need = 2 * D * -(-n // per)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=x.device)
+    assert workspace.dtype == torch.float64 and workspace.device == x.device and workspace.numel() >= need
+    check(_native.lib().pfrl_obs_stats_update(_ptr(x), n, D, _ptr(mean), _ptr(var), _ptr(count),
+                                              -1 if until is None else max(0, math.ceil(until)), _ptr(workspace),
+                                              workspace.numel(), _stream()), "obs_stats_update")
 
 
 # ---------------------------------------------------------------------------------------------

@@ -11,6 +11,11 @@ of the windows in microseconds per call for both variants, and the largest diffe
                                                  # PFRL_MLP_WIDE=1 against 0, each as replays of a captured graph
     python tools/mlp_time.py --fvp               # TRPO's Fisher-vector product: ops.gaussian_mlp_fisher (three or four
                                                  # launches) against autograd's double backward, us per product
+    python tools/mlp_time.py --norm              # an observation normaliser in front of the policy / value pair:
+                                                 # normalised in the launch's loader (PFRL_OBS_NORM_LOADER=1) against
+                                                 # the torch expressions in front of it (0, the launches of the parent
+                                                 # commit), as replays of a captured graph; then ``experience``,
+                                                 # kernel route against module route
 """
 import argparse
 import copy
@@ -166,6 +171,64 @@ def fvp_main(args):
         print(json.dumps(rec), flush=True)
 
 
+def alternate(fns, args, per_call=1):
+    """{name: mean / min / max us per call} of alternating windows."""
+    for f in fns.values():
+        window(f, 20)
+    calls = {k: max(5, int(args.window_ms * 1e3 / (per_call * window(f, 20)))) for k, f in fns.items()}
+    times = {k: [] for k in fns}
+    for _ in range(args.windows):
+        for k, f in fns.items():
+            times[k].append(window(f, calls[k]) / per_call)
+    return {k + "_us": dict(mean=sum(v) / len(v), min=min(v), max=max(v)) for k, v in times.items()}
+
+
+def norm_main(args):
+    """The acting step behind the gather (normaliser + policy / value pair, no_grad) as replays of a captured graph of 20
+    steps, loader on against off; then ``EmpiricalNormalization.experience`` eagerly, kernel route against module route."""
+    from pfrl_amd.agents import _capture
+    from pfrl_amd.nn import EmpiricalNormalization
+    from pfrl_amd.nn.mfma_linear import _fuse_small_mlps
+
+    class Holder:
+        pool = None
+
+    for obs in (11, 376):
+        torch.manual_seed(0)
+        model = _fuse_small_mlps(make(obs, 6, nn.Tanh, True).cuda())
+        n = EmpiricalNormalization(obs, clip_threshold=5).cuda()
+        n.experience(3 + 2 * torch.randn(4096, obs, device="cuda"))
+        for rows in (1, 64, 2048):
+            x = 3 + 2 * torch.randn(rows, obs, device="cuda")
+
+            def fn():
+                with torch.no_grad():
+                    return torch.cat(model.forward_normalized(x, n), 1)
+
+            graphs, outs = {}, {}
+            for k, env in (("loader", "1"), ("in_front", "0")):
+                os.environ["PFRL_OBS_NORM_LOADER"] = env
+                outs[k] = fn().clone()
+                _capture.warm_up("cuda", lambda i: fn())
+                graphs[k] = _capture.capture(Holder, lambda: [fn() for _ in range(20)])[0]
+            os.environ.pop("PFRL_OBS_NORM_LOADER")
+            rec = dict(case="acting step", obs=obs, rows=rows, equal=bool(torch.equal(outs["loader"], outs["in_front"])))
+            rec.update(alternate({k: g.replay for k, g in graphs.items()}, args, per_call=20))
+            print(json.dumps(rec), flush=True)
+    for obs in (11, 376):
+        x = 3 + 2 * torch.randn(2048, obs, device="cuda")
+        mods = {k: EmpiricalNormalization(obs).cuda() for k in ("kernel", "module")}
+
+        def learn(k):
+            os.environ["PFRL_OBS_STATS_KERNEL"] = "1" if k == "kernel" else "0"
+            mods[k].experience(x)
+
+        rec = dict(case="experience", obs=obs, rows=2048)
+        rec.update(alternate({k: (lambda k=k: learn(k)) for k in mods}, args))
+        os.environ.pop("PFRL_OBS_STATS_KERNEL")
+        print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, nargs="+", default=[1, 64, 2048, 16384])
@@ -176,7 +239,10 @@ def main():
     ap.add_argument("--window-ms", type=float, default=20.0)
     ap.add_argument("--wide", action="store_true")
     ap.add_argument("--fvp", action="store_true")
+    ap.add_argument("--norm", action="store_true")
     args = ap.parse_args()
+    if args.norm:
+        return norm_main(args)
     if args.wide:
         return wide_main(args)
     if args.fvp:
